@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the path-scoring hot path (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload config3]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload config3] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one batch: every candidate path of
 the workload scored against every alignment (reference src/eval.cpp:67-108 once
@@ -15,6 +15,13 @@ RCCL all-reduce inside the step: the same total work for every N ("strong").
 
 Rank 0 prints ONE JSON line; see DESIGN.md "Measurement" for how `roofline`,
 `cpu_baseline` and `search_mode` are defined.
+
+--dump-outputs DIR: rank 0 also writes what the last timed step computed -- the
+per-path counters a caller of gfal_scorer_score_device receives, summed over the
+ranks -- as DIR/bad.npy, DIR/good.npy and DIR/unaligned.npy (float64, exact for
+uint32; 3 x 8 bytes per candidate path).  The workload is seeded, so the same
+arguments give the same inputs on every run and two builds can be compared
+output for output.
 """
 import argparse
 import gc
@@ -218,6 +225,14 @@ def cpu_fast(t, bad, good, una, n_paths=64):
                       "quantiles) x all %d alignments of %s; every fourth of them on one core" % (n_paths, t.N, t.name)}
 
 
+def dump_outputs(out_dir, counts, P):
+    """The [3P] uint32 counters of one step as three float64 arrays (exact; P = 10 000
+    for config3 is 240 kB in all, config5 the same: far below 64 MB, no sampling)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for k, name in enumerate(("bad", "good", "unaligned")):
+        np.save(os.path.join(out_dir, name + ".npy"), counts[k * P:(k + 1) * P].astype(np.float64))
+
+
 def spawn_ranks(args):
     """`python bench.py --gpus N` without a launcher: N fresh rank processes of this very
     script (children, never a re-exec; the parent has not imported torch or touched a GPU),
@@ -266,7 +281,11 @@ def main():
     ap.add_argument("--workload", default="config3")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-search-mode", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the counters of the last timed step as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_ranks(args)          # (does not return)
@@ -347,6 +366,8 @@ def main():
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
     gc.enable()
+    # the counters of the last timed step, before the profiled steps below overwrite them
+    last_counts = d_counts.cpu().numpy().view(np.uint32) if args.dump_outputs else None
     sc.sync_status()
     info = sc.info()
     # the phases of a step (scan phase, exact DP, whole call): a few more steps with every
@@ -367,6 +388,9 @@ def main():
 
     counts = d_counts.cpu().numpy().view(np.uint32)
     bad, good, una = counts[:P], counts[P:2 * P], counts[2 * P:]
+
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last_counts, P)
 
     if rank == 0:
         ms_per_step = 1e3 * elapsed / args.steps

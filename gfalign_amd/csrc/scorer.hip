@@ -6230,6 +6230,14 @@ static int create_impl(const int32_t *aln_off, const int32_t *aln_steps, int64_t
     // worklist: at least one entry per alignment, so a single path always fits
     if (const char *env = getenv("GFAL_DP_SYS_LIMIT")) s->dp_sys_limit = (uint32_t)atoll(env);
     if (const char *env = getenv("GFAL_GRAPHS")) s->use_graphs = atoi(env) != 0;
+    // graph replay is built and tested on the HIP runtime of the headers it was compiled
+    // with; an older runtime loaded into the process (the ROCm 7.0 one that PyTorch bundles,
+    // say) faults inside the captured call, so there the call launches directly
+    if (s->use_graphs) {
+        int runtime_version = 0;
+        if (hipRuntimeGetVersion(&runtime_version) != hipSuccess || runtime_version < HIP_VERSION)
+            s->use_graphs = false;
+    }
     s->wl_capacity = (uint32_t)std::max<int64_t>(own_aln, (int64_t)1 << 22);
     if (const char *env = getenv("GFAL_DEBUG_WL_CAPACITY"))   // tests: force the overflow path
         s->wl_capacity = (uint32_t)std::max<int64_t>(own_aln, atoll(env));

@@ -15,6 +15,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -27,12 +28,12 @@ def _free_port():
         return s.getsockname()[1]
 
 
-def _bench(extra_env, launcher, gpus=1):
+def _bench(extra_env, launcher, gpus=1, extra_args=()):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", **extra_env)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):       # (a plain `python bench.py` starts without them)
         env.pop(k, None)
     cmd = launcher + [os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "2", "--warmup", "1",
-                      "--workload", "config2", "--no-cpu-baseline", "--no-search-mode"]
+                      "--workload", "config2", "--no-cpu-baseline", "--no-search-mode"] + list(extra_args)
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     line = [l for l in p.stdout.splitlines() if l.startswith("{")][-1]
@@ -70,3 +71,19 @@ def test_a_failing_rank_fails_the_run():
                         "--workload", "config2", "--no-cpu-baseline", "--no-search-mode"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert p.returncode != 0
+
+
+def test_dump_outputs_are_the_counters_of_the_timed_step(tmp_path):
+    """--dump-outputs DIR: the per-path counters of the last timed step as float64 .npy
+    files, the same counters the JSON line's counter_checksum is taken over."""
+    from gfalign_amd import scorer
+    if scorer.device_count() < 1:
+        pytest.fail("needs an MI355X")
+    out = _bench({}, [sys.executable], extra_args=["--dump-outputs", str(tmp_path)])
+    assert out["steps"] == 2
+    arrays = {name: np.load(tmp_path / (name + ".npy")) for name in ("bad", "good", "unaligned")}
+    for a in arrays.values():
+        assert a.dtype == np.float64 and a.shape == (1000,)          # config2: 1 000 candidate paths
+        assert np.all(a >= 0) and np.array_equal(a, np.floor(a))
+    checksum = int(arrays["bad"].sum()) * 3 + int(arrays["good"].sum()) * 5 + int(arrays["unaligned"].sum()) * 7
+    assert checksum == out["config"]["counter_checksum"]

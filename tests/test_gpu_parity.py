@@ -301,20 +301,41 @@ def test_more_than_32k_paths_in_one_batch(gpu):
     assert np.array_equal(una[sample], eu)
 
 
-def test_graph_replay_gives_the_same_counters(gpu, monkeypatch):
+_GRAPH_REPLAY = """
+import random, sys
+import numpy as np
+sys.path[:0] = [ROOT, TESTS]
+import oracle
+from gfalign_amd.scorer import Scorer
+from helpers import csr, walk_case
+assert "torch" not in sys.modules
+rnd = random.Random(71)
+alns, paths = walk_case(rnd, 25, 150, 900, 60, 14)
+aoff, ast = csr(alns)
+with Scorer(aoff, ast, 32) as sc:
+    for lo, hi in ((0, 7), (7, 40), (3, 4), (0, 60), (10, 11)):
+        poff, pst = csr(paths[lo:hi])
+        got = sc.evaluate_paths(poff, pst, True)
+        exp = oracle.evaluate_paths(aoff, ast, poff, pst, True)
+        for g, e in zip(got, exp):
+            assert np.array_equal(g, e), (lo, hi)
+print("OK")
+"""
+
+
+def test_graph_replay_gives_the_same_counters(gpu):
     """GFAL_GRAPHS=1: the blocking call captures its launches into a HIP graph and
-    updates the executable from call to call (batch shapes change)."""
-    rnd = random.Random(71)
-    alns, paths = walk_case(rnd, 25, 150, 900, 60, 14)
-    aoff, ast = csr(alns)
-    monkeypatch.setenv("GFAL_GRAPHS", "1")
-    with Scorer(aoff, ast, 32) as sc:
-        for lo, hi in ((0, 7), (7, 40), (3, 4), (0, 60), (10, 11)):
-            poff, pst = csr(paths[lo:hi])
-            got = sc.evaluate_paths(poff, pst, True)
-            exp = oracle.evaluate_paths(aoff, ast, poff, pst, True)
-            for g, e in zip(got, exp):
-                assert np.array_equal(g, e)
+    updates the executable from call to call (batch shapes change).  In a fresh
+    process without torch: the library takes graphs only on a HIP runtime at least as
+    new as the one it was built with, and the suite's process has loaded torch's
+    bundled runtime by the time this runs (tests/test_multi_rank.py imports torch)."""
+    import subprocess
+    import sys
+    tests = os.path.dirname(os.path.abspath(__file__))
+    code = "ROOT, TESTS = %r, %r\n" % (os.path.dirname(tests), tests) + _GRAPH_REPLAY
+    p = subprocess.run([sys.executable] + (["-s"] if sys.flags.no_user_site else []) + ["-c", code],
+                       env=dict(os.environ, GFAL_GRAPHS="1"), capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0 and p.stdout.strip() == "OK", p.stdout[-2000:] + p.stderr[-2000:]
 
 
 def test_more_shards_than_items(gpu):
