@@ -17,6 +17,7 @@
 #include <cstring>
 #include <iomanip>
 #include <iostream>
+#include <memory>
 #include <mutex>
 #include <set>
 #include <sstream>
@@ -210,6 +211,43 @@ std::string b_row(const Rows &r, const Graph &g)   // include/alignments.h:113-1
     return s;
 }
 
+// The same row from the traceback's ops (include/gfalign_scorer.h: 0 diagonal with equal
+// steps, 1 diagonal with different ones, 2 up, 3 left) as the device returns them, with
+// no table: A and the oriented B are walked alongside.  `score` receives what the
+// reference's traceback charges for them (src/alignments.cpp:516-550), walked from the
+// last column as it does: an up move costs only after some B step was taken, row 0 and
+// column 0 are free.
+std::string b_row_from_ops(const std::vector<Step> &A, const std::vector<Step> &B, const uint8_t *ops,
+                           size_t n_ops, const Graph &g, int &score)
+{
+    std::string s;
+    size_t i = 0, j = 0;
+    for (size_t t = 0; t < n_ops; ++t) {
+        if (ops[t] == 2) {
+            s.append(g.headers[(size_t)A[i++].id].size() + 1, '-');
+        } else {
+            const Step &y = B[j++];
+            if (ops[t] == 0) s.append(g.headers[(size_t)y.id].size() + 1, '.');
+            else s += g.headers[(size_t)y.id] + y.orientation;
+            if (ops[t] != 3) ++i;
+        }
+        s += ',';
+    }
+    score = 0;
+    int taken = 0;
+    for (size_t t = n_ops; t-- > 0;) {
+        const int op = ops[t];
+        if (i != 0 && j != 0) {
+            if (op <= 1) score -= op, ++taken;
+            else if (op == 2) score -= taken > 0;
+            else score -= 1, ++taken;
+        }
+        if (op != 3) --i;
+        if (op != 2) --j;
+    }
+    return s;
+}
+
 int run_eval_path(const Options &o, const Graph &g, const std::vector<GafRecord> &recs)
 {
     // src/eval.cpp:203-227: split on ',' / ';', last char = orientation
@@ -265,17 +303,33 @@ int run_eval_path(const Options &o, const Graph &g, const std::vector<GafRecord>
     std::vector<int32_t> off{0, (int32_t)pst.size()};
     std::vector<uint32_t> bad, good;
     if (!scorer.score(off, pst, false, bad, good)) return 1;              // :238
-    std::vector<int32_t> fw, rc;
-    if (!scorer.pair_scores(pst, fw, rc)) return 1;
-    // One row per alignment (:100-102).  The scores come from the GPU; the gapped
-    // row text needs the traceback itself, which is rendered on the host -- for a
-    // 10 M-alignment GAF that is tens of GB of text, so blocks of alignments are
-    // rendered on all cores and written in order.
+    // One row per alignment (:100-102).  The scores and the traceback of the winning
+    // orientation come from the GPU, the ops of a block of alignments at a time; the
+    // text is rendered from them -- for a 10 M-alignment GAF that is tens of GB of
+    // text, so blocks are rendered on all cores and written in order.
+    // GFALIGN_HOST_TRACEBACK=1: the traceback is filled again on the host instead
+    // (traceback_rows; same output).
+    const bool host_traceback =
+        getenv("GFALIGN_HOST_TRACEBACK") != nullptr && atoi(getenv("GFALIGN_HOST_TRACEBACK")) != 0;
+    std::vector<int32_t> fw, rc, ops_len;
+    if (host_traceback ? !scorer.pair_scores(pst, fw, rc)
+                       : !scorer.pair_alignment_lengths(pst, fw, rc, ops_len))
+        return 1;
+    // the ops come in chunks of 32 blocks, one scorer call each, fetched by one thread
+    // ahead of the renderers (as far as their 64-block window reaches); a chunk is freed
+    // with its last block
+    struct OpsChunk {
+        std::vector<int64_t> off;             // alignment k's ops: [off[k - k0], off[k - k0 + 1])
+        std::vector<uint8_t> ops;
+        size_t blocks_left = 0;
+    };
     const size_t n_rec = recs.size();
     const size_t block = 2048;
     const size_t n_blocks = (n_rec + block - 1) / block;
     unsigned n_threads = std::min<unsigned>(16, std::max(1u, std::thread::hardware_concurrency()));
     if (n_blocks < 4) n_threads = 1;
+    const size_t chunk_blocks = 32;
+    std::vector<std::shared_ptr<OpsChunk>> chunks((n_blocks + chunk_blocks - 1) / chunk_blocks);
     std::vector<std::string> text(n_blocks);
     std::vector<char> ready(n_blocks, 0);
     std::string failure;
@@ -292,8 +346,17 @@ int run_eval_path(const Options &o, const Graph &g, const std::vector<GafRecord>
                 if (!failure.empty()) return;
             }
             std::string out;
-            const size_t hi = std::min(n_rec, (blk + 1) * block);
-            for (size_t k = blk * block; k < hi; ++k) {
+            const size_t lo = blk * block, hi = std::min(n_rec, (blk + 1) * block);
+            const size_t c = blk / chunk_blocks;
+            const size_t c_lo = c * chunk_blocks * block;
+            std::shared_ptr<OpsChunk> ch;
+            if (!host_traceback) {
+                std::unique_lock<std::mutex> lk(mu);
+                cv.wait(lk, [&] { return chunks[c] || !failure.empty(); });
+                if (!failure.empty()) return;
+                ch = chunks[c];
+            }
+            for (size_t k = lo; k < hi; ++k) {
                 B.clear();
                 for (int32_t t = packed.off[k]; t < packed.off[k + 1]; ++t)
                     B.push_back({packed.steps[(size_t)t] >> 1, (packed.steps[(size_t)t] & 1) ? '-' : '+'});
@@ -302,17 +365,26 @@ int run_eval_path(const Options &o, const Graph &g, const std::vector<GafRecord>
                     std::reverse(B.begin(), B.end());
                     for (auto &st : B) st.orientation = (st.orientation == '+') ? '-' : '+';
                 }
-                Rows rows = traceback_rows(path, B);
+                std::string row;
+                int score;
+                if (host_traceback) {
+                    Rows rows = traceback_rows(path, B);
+                    row = b_row(rows, g);
+                    score = rows.score;
+                } else {
+                    const int64_t *off = ch->off.data() + (k - c_lo);
+                    row = b_row_from_ops(path, B, ch->ops.data() + off[0], (size_t)(off[1] - off[0]), g, score);
+                }
                 const int32_t best = std::max(fw[k], rc[k]);
-                if (rows.score != best) {
+                if (score != best) {
                     std::lock_guard<std::mutex> lk(mu);
                     if (failure.empty())
                         failure = "device score " + std::to_string(best) + " != rendered score " +
-                                  std::to_string(rows.score) + " for " + recs[k].qname;
+                                  std::to_string(score) + " for " + recs[k].qname;
                     cv.notify_all();
                     return;
                 }
-                out += b_row(rows, g);
+                out += row;
                 out += '\t';
                 out += recs[k].qname;
                 out += '\t';
@@ -320,12 +392,39 @@ int run_eval_path(const Options &o, const Graph &g, const std::vector<GafRecord>
                 out += '\n';
             }
             std::lock_guard<std::mutex> lk(mu);
+            if (ch && --ch->blocks_left == 0) chunks[c].reset();
             text[blk] = std::move(out);
             ready[blk] = 1;
             cv.notify_all();
         }
     };
+    auto fetch = [&]() {                      // the only thread that uses the scorer from here on
+        for (size_t c = 0; c < chunks.size(); ++c) {
+            {
+                std::unique_lock<std::mutex> lk(mu);
+                cv.wait(lk, [&] { return c * chunk_blocks < written + 64 || !failure.empty(); });
+                if (!failure.empty()) return;
+            }
+            const size_t c_lo = c * chunk_blocks * block, c_hi = std::min(n_rec, (c + 1) * chunk_blocks * block);
+            auto fresh = std::make_shared<OpsChunk>();
+            fresh->off.assign(c_hi - c_lo + 1, 0);
+            for (size_t k = c_lo; k < c_hi; ++k) fresh->off[k - c_lo + 1] = fresh->off[k - c_lo] + ops_len[k];
+            fresh->ops.resize((size_t)fresh->off[c_hi - c_lo]);
+            fresh->blocks_left = std::min(n_blocks, (c + 1) * chunk_blocks) - c * chunk_blocks;
+            const bool ok = scorer.pair_alignment_ops(pst, (int64_t)c_lo, (int64_t)c_hi, fresh->off, fresh->ops);
+            std::lock_guard<std::mutex> lk(mu);
+            if (!ok) {
+                if (failure.empty())
+                    failure = "traceback ops of alignments " + std::to_string(c_lo) + ".." + std::to_string(c_hi);
+                cv.notify_all();
+                return;
+            }
+            chunks[c] = std::move(fresh);
+            cv.notify_all();
+        }
+    };
     std::vector<std::thread> pool;
+    if (!host_traceback) pool.emplace_back(fetch);
     for (unsigned t = 0; t < n_threads; ++t) pool.emplace_back(render);
     for (size_t blk = 0; blk < n_blocks; ++blk) {
         std::string out;

@@ -37,7 +37,11 @@
 //   k_dp_sys    the same for short worklists (search-sized batches), one table
 //               column per lane: the latency of a single fill decides there.
 //   k_pairs     the same exact DP for every alignment of one path, both
-//               orientations (evalPath's per-alignment scores).
+//               orientations (evalPath's per-alignment scores; optionally the
+//               length of the winning orientation's traceback).
+//   k_pair_ops  the traceback itself, one op per printed column, for a list
+//               of alignments (evalPath's rows): the winner's fill again with
+//               every cell's move kept, then the walk back.
 //   k_child     search mode: a candidate scored from its parent (stored on the
 //               device) through two inverted lists, a content table and the
 //               DP verdicts remembered per stored path; k_dp_small decides what
@@ -2182,20 +2186,30 @@ __device__ __forceinline__ uint32_t pack_cell(int dp, int x)
 __device__ __forceinline__ int cell_dp(uint32_t c) { return (int)(int16_t)(c & 0xFFFFu); }
 __device__ __forceinline__ int cell_x(uint32_t c) { return (int)(int16_t)(c >> 16); }
 
-__device__ __forceinline__ int traceback_score(const StepsA &A, const StepsB &B,
-                                               uint32_t *row, int stride)
+// The same fill carries, in place of X, the number of moves of the traceback (LENGTH):
+// len = 1 + len[predecessor] at an interior cell, j at exit cell (0, j), i at (i, 0) --
+// what evalPath's printed row is long.  MOVES additionally keeps the move chosen at
+// every interior cell (0 diagonal, 1 up, 2 left; 2 bits, 16 columns to a word, row
+// by row) at moves[word * mstride], so that the traceback can be walked afterwards
+// (k_pair_ops).  Returns the score, or with LENGTH the move count.
+template <bool LENGTH, bool MOVES>
+__device__ __forceinline__ int traceback_fill(const StepsA &A, const StepsB &B,
+                                              uint32_t *row, int stride,
+                                              uint32_t *moves, int mstride)
 {
     const int n = A.n, m = B.m;
     for (int j = 0; j <= m; ++j) {
         int v = (j <= n) ? -j : 0;           // :500, row 0 reaches column n only
-        row[(size_t)j * stride] = pack_cell(v, v);
+        row[(size_t)j * stride] = pack_cell(v, LENGTH ? j : v);
     }
+    size_t word = 0;
     for (int i = 1; i <= n; ++i) {
         const uint32_t ai = A.step[i - 1];
         uint32_t c = row[0];
         int diag_dp = cell_dp(c), diag_x = cell_x(c);
-        row[0] = pack_cell(0, 0);            // column 0 is never written: 0
-        int left_dp = 0, left_x = 0;
+        row[0] = pack_cell(0, LENGTH ? i : 0);   // column 0 is never written: 0
+        int left_dp = 0, left_x = LENGTH ? i : 0;
+        uint32_t acc = 0;
         for (int j = 1; j <= m; ++j) {
             c = row[(size_t)j * stride];
             const int up_dp = cell_dp(c), up_x = cell_x(c);
@@ -2205,9 +2219,19 @@ __device__ __forceinline__ int traceback_score(const StepsA &A, const StepsB &B,
             const int l = left_dp - 1;
             const int v = max(d, max(u, l));
             int x;
-            if (v == d) x = diag_x;                    // :527
-            else if (up_dp >= left_dp) x = up_x;       // :534
-            else x = left_x;                           // :541
+            uint32_t mv;
+            if (v == d) x = diag_x, mv = 0;                   // :527
+            else if (up_dp >= left_dp) x = up_x, mv = 1;      // :534
+            else x = left_x, mv = 2;                          // :541
+            if (LENGTH) x += 1;
+            if (MOVES) {
+                acc |= mv << (2 * ((j - 1) & 15));
+                if (((j - 1) & 15) == 15 || j == m) {
+                    moves[word * mstride] = acc;
+                    ++word;
+                    acc = 0;
+                }
+            }
             row[(size_t)j * stride] = pack_cell(v, x);
             diag_dp = up_dp;
             diag_x = up_x;
@@ -2216,7 +2240,13 @@ __device__ __forceinline__ int traceback_score(const StepsA &A, const StepsB &B,
         }
     }
     uint32_t c = row[(size_t)m * stride];
-    return cell_dp(c) - cell_x(c);
+    return LENGTH ? cell_x(c) : cell_dp(c) - cell_x(c);
+}
+
+__device__ __forceinline__ int traceback_score(const StepsA &A, const StepsB &B,
+                                               uint32_t *row, int stride)
+{
+    return traceback_fill<false, false>(A, B, row, stride, nullptr, 0);
 }
 
 // Row state: one word per column per thread.  Short alignments keep it in LDS
@@ -2996,12 +3026,14 @@ __global__ __launch_bounds__(DP_THREADS) void k_dp_long(DpArgs a)
     }
 }
 
-template <bool ROWS_IN_LDS>
+// LENGTHS: also the move count of the winning orientation's traceback (src/eval.cpp:100:
+// fw is shown only when strictly greater), a third fill of that orientation.
+template <bool ROWS_IN_LDS, bool LENGTHS>
 __global__ __launch_bounds__(DP_THREADS) void k_pairs(
     Items items, const int32_t *__restrict__ slot_orig,
     const uint16_t *__restrict__ image, ImageLayout L,
     uint32_t *__restrict__ row_scratch, int32_t *__restrict__ fw,
-    int32_t *__restrict__ rc)
+    int32_t *__restrict__ rc, int32_t *__restrict__ len)
 {
     int stride;
     uint32_t *row = dp_row<ROWS_IN_LDS>(row_scratch, stride);
@@ -3015,9 +3047,109 @@ __global__ __launch_bounds__(DP_THREADS) void k_pairs(
         const uint32_t it = (uint32_t)(s >> 6), ln = (uint32_t)(s & 63);
         StepsB B{items.steps + (size_t)items.base[it] * WAVE + ln,
                  (int)items.len[it], 0u};
-        fw[orig] = traceback_score(A, B, row, stride);
+        const int f = traceback_score(A, B, row, stride);
+        fw[orig] = f;
         B.flip = 1u;
-        rc[orig] = traceback_score(A, B, row, stride);
+        const int r = traceback_score(A, B, row, stride);
+        rc[orig] = r;
+        if (LENGTHS) {
+            B.flip = f > r ? 0u : 1u;
+            len[orig] = traceback_fill<true, false>(A, B, row, stride, nullptr, 0);
+        }
+    }
+}
+
+// One entry of k_pair_ops' list: a lane of the items and where its ops go.
+struct TraceEntry {
+    long long dst;   // first op in the output buffer
+    int32_t slot;    // item * 64 + lane
+    int32_t cap;     // ops expected (the caller's slot); a walk of another length is an error
+};
+
+// The traceback of the winning orientation, as one op per column of the printed
+// alignment (include/gfalign_scorer.h: 0 diagonal with equal steps, 1 diagonal with
+// different ones, 2 up, 3 left), for a list of lanes sorted by slot (the lanes of one
+// item stay together: one m per wave, coalesced move stores).  Per lane: fw and rc as
+// k_pairs, then the winner's fill again with every cell's move kept -- in LDS behind
+// the rows (MOVES_IN_LDS) or in `move_scratch`, [word][lane] either way, n * ceil(m/16)
+// words per lane -- then the walk back from (n, m) (src/alignments.cpp:516-550), whose
+// ops are written last to first.  A lane writes nothing outside [dst, dst + cap); a
+// walk of any other length than cap counts in *bad.
+template <bool ROWS_IN_LDS, bool MOVES_IN_LDS>
+__global__ __launch_bounds__(DP_THREADS) void k_pair_ops(
+    Items items, const uint16_t *__restrict__ image, ImageLayout L,
+    const TraceEntry *__restrict__ ent, int n_ent, int row_words,
+    uint32_t *__restrict__ row_scratch, uint32_t *__restrict__ move_scratch,
+    uint8_t *__restrict__ ops, uint32_t *__restrict__ bad)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t dp_lds[];
+    int stride;
+    uint32_t *row = dp_row<ROWS_IN_LDS>(row_scratch, stride);
+    uint32_t *mv;
+    int mstride;
+    if (MOVES_IN_LDS) {
+        mv = dp_lds + (size_t)row_words * DP_THREADS + threadIdx.x;
+        mstride = DP_THREADS;
+    } else {
+        mv = move_scratch + (size_t)blockIdx.x * DP_THREADS + threadIdx.x;
+        mstride = gridDim.x * DP_THREADS;
+    }
+    const uint16_t *astep = image + L.step_at();
+    const int n = (int)image[L.len_at()];
+    for (long long e0 = (long long)blockIdx.x * DP_THREADS; e0 < n_ent;
+         e0 += (long long)gridDim.x * DP_THREADS) {
+        const long long e = e0 + threadIdx.x;
+        const bool live = e < n_ent;
+        TraceEntry t{0, 0, 0};
+        if (live) t = ent[e];
+        const uint32_t it = (uint32_t)t.slot >> 6, ln = (uint32_t)t.slot & 63u;
+        // a dead lane fills an empty table and stays with the wave
+        StepsA A{astep, live ? n : 0};
+        StepsB B{items.steps + (size_t)items.base[it] * WAVE + ln,
+                 live ? (int)items.len[it] : 0, 0u};
+        const int f = traceback_score(A, B, row, stride);
+        B.flip = 1u;
+        const int r = traceback_score(A, B, row, stride);
+        B.flip = f > r ? 0u : 1u;
+        const int len = traceback_fill<true, true>(A, B, row, stride, mv, mstride);
+        if (!live) continue;
+        if (len != t.cap) {
+            atomicAdd(bad, 1u);
+            continue;
+        }
+        const int m = B.m, wpr = (m + 15) >> 4;
+        uint8_t *out = ops + t.dst;
+        int i = n, j = m, k = len;
+        while (i != 0 || j != 0) {
+            if (k == 0) {                   // longer than cap: stop at the slot's start
+                atomicAdd(bad, 1u);
+                break;
+            }
+            uint32_t op;
+            if (i == 0) {                   // :517-520
+                op = 3;
+                --j;
+            } else if (j == 0) {            // :521-524
+                op = 2;
+                --i;
+            } else {
+                const uint32_t w = mv[((size_t)(i - 1) * wpr + ((j - 1) >> 4)) * mstride];
+                const uint32_t c = (w >> (2 * ((j - 1) & 15))) & 3u;
+                if (c == 0) {
+                    op = (astep[i - 1] == B.at(j - 1)) ? 0u : 1u;
+                    --i;
+                    --j;
+                } else if (c == 1) {
+                    op = 2;
+                    --i;
+                } else {
+                    op = 3;
+                    --j;
+                }
+            }
+            out[--k] = (uint8_t)op;
+        }
+        if (k != 0) atomicAdd(bad, 1u);
     }
 }
 
@@ -5288,6 +5420,15 @@ struct gfal_scorer {
     uint32_t *d_wl_bins = nullptr;     // [3][N_CLASSES * n_paths]: hist | offsets | cursor
     size_t wl_bins_cap = 0;
     uint32_t *d_rows = nullptr;        // DP row scratch
+    // gfal_scorer_pair_alignment_ops: the lane of every caller alignment (-1: zero steps)
+    // and every item's length, taken from the device at the first call; the per-call
+    // list, ops and move scratch of k_pair_ops
+    std::vector<int32_t> slot_of;
+    std::vector<uint16_t> h_item_len;
+    TraceEntry *d_trace_ent = nullptr;
+    uint8_t *d_trace_ops = nullptr;
+    uint32_t *d_trace_moves = nullptr;
+    size_t trace_ent_cap = 0, trace_ops_cap = 0, trace_moves_cap = 0;
     uint16_t *d_images = nullptr;
     size_t images_cap = 0;             // uint16 units
 
@@ -5410,7 +5551,8 @@ void free_scorer(gfal_scorer *s)
                     s->d_counts,     s->d_inv_off,   s->d_inv_ent,    s->d_ct_key,
                     s->d_ct_hash,    s->d_ct_mult,   s->d_pair_bits, s->d_st_steps,   s->d_st_len,
                     s->d_st_pass,    s->d_st_g1,     s->d_child_in,   s->d_child_tmp,
-                    s->d_st_bits,    s->d_st_bitsok, s->d_wl_pos,     s->d_wl_pos_sorted};
+                    s->d_st_bits,    s->d_st_bitsok, s->d_wl_pos,     s->d_wl_pos_sorted,
+                    s->d_trace_ent,  s->d_trace_ops, s->d_trace_moves};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (s->graph_exec) (void)hipGraphExecDestroy(s->graph_exec);
@@ -7935,19 +8077,33 @@ int gfal_group_score(gfal_group *g, const int32_t *path_off, const int32_t *path
     return gfal_group_score_end(g, bad, good, unaligned);
 }
 
-static int pair_scores_impl(gfal_scorer *s, const int32_t *path_steps, int32_t n,
-                            int32_t *fw, int32_t *rc_out);
+static int pair_impl(gfal_scorer *s, const int32_t *path_steps, int32_t n,
+                     int32_t *fw, int32_t *rc_out, int32_t *ops_len);
+static int pair_ops_impl(gfal_scorer *s, const int32_t *path_steps, int32_t n, int64_t k0,
+                         int64_t k1, const int64_t *ops_off, uint8_t *ops);
 
 int gfal_scorer_pair_scores(gfal_scorer *s, const int32_t *path_steps, int32_t n,
                             int32_t *fw, int32_t *rc_out)
 {
-    return no_throw([&] { return pair_scores_impl(s, path_steps, n, fw, rc_out); });
+    return no_throw([&] { return pair_impl(s, path_steps, n, fw, rc_out, nullptr); });
 }
 
-static int pair_scores_impl(gfal_scorer *s, const int32_t *path_steps, int32_t n,
-                            int32_t *fw, int32_t *rc_out)
+int gfal_scorer_pair_alignment_lengths(gfal_scorer *s, const int32_t *path_steps, int32_t n,
+                                       int32_t *fw, int32_t *rc_out, int32_t *ops_len)
 {
-    if (!s || !path_steps || !fw || !rc_out) return GFAL_E_ARG;
+    if (!ops_len) return GFAL_E_ARG;
+    return no_throw([&] { return pair_impl(s, path_steps, n, fw, rc_out, ops_len); });
+}
+
+int gfal_scorer_pair_alignment_ops(gfal_scorer *s, const int32_t *path_steps, int32_t n,
+                                   int64_t k0, int64_t k1, const int64_t *ops_off, uint8_t *ops)
+{
+    return no_throw([&] { return pair_ops_impl(s, path_steps, n, k0, k1, ops_off, ops); });
+}
+
+// What the pair calls share: argument checks and the path's image (k_prep) on s->stream.
+static int pair_prep(gfal_scorer *s, const int32_t *path_steps, int32_t n, ImageLayout *out)
+{
     if (n < 1 || n > GFAL_MAX_STEPS) return GFAL_E_RANGE;
     for (int32_t i = 0; i < n; ++i) {
         int32_t st = path_steps[i];
@@ -7977,46 +8133,73 @@ static int pair_scores_impl(gfal_scorer *s, const int32_t *path_steps, int32_t n
                        s->n_empty, 0, L, nullptr, s->d_images, s->d_counts, s->d_status, nullptr, nullptr,
                        PrepChild());
     HIP_TRY(hipGetLastError());
+    *out = L;
+    return GFAL_OK;
+}
+
+static Items scorer_items(const gfal_scorer *s)
+{
+    return Items{s->d_item_steps, s->d_item_base, s->d_item_len, s->d_item_pairs,
+                 s->d_item_pbase, s->n_items, s->d_item_common, s->d_item_hdr, s->d_item_weight};
+}
+
+// ops_len == NULL: gfal_scorer_pair_scores; else also the move counts (k_pairs<, true>)
+static int pair_impl(gfal_scorer *s, const int32_t *path_steps, int32_t n,
+                     int32_t *fw, int32_t *rc_out, int32_t *ops_len)
+{
+    if (!s || !path_steps || !fw || !rc_out) return GFAL_E_ARG;
+    ImageLayout L;
+    int rc = pair_prep(s, path_steps, n, &L);
+    if (rc != GFAL_OK || s->n_aln == 0) return rc;
 
     // device results are indexed like the caller's alignments (all shards)
     const size_t n_in = (size_t)s->n_aln_in;
-    int32_t *d_fw = nullptr, *d_rc = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d_fw), n_in * sizeof(int32_t)));
-    hipError_t e2 = hipMalloc(reinterpret_cast<void **>(&d_rc), n_in * sizeof(int32_t));
+    const int n_out = ops_len ? 3 : 2;
+    int32_t *d_out = nullptr;    // fw | rc [| len]
+    hipError_t e2 = hipMalloc(reinterpret_cast<void **>(&d_out), (size_t)n_out * n_in * sizeof(int32_t));
     if (e2 != hipSuccess) {
-        (void)hipFree(d_fw);
         set_err("hipMalloc failed: %s", hipGetErrorString(e2));
         return GFAL_E_NOMEM;
     }
-    // zero-step alignments: both tracebacks are free (score 0)
+    int32_t *d_fw = d_out, *d_rc = d_out + n_in, *d_len = ops_len ? d_out + 2 * n_in : nullptr;
+    // zero-step alignments: both tracebacks are free (score 0); theirs is n moves
+    // down column 0 (src/alignments.cpp:521-524)
     unsigned fill_blocks = (unsigned)((n_in + 255) / 256);
     hipLaunchKernelGGL(k_fill_i32, dim3(fill_blocks), dim3(256), 0, s->stream, d_fw,
                        (long long)n_in, 0);
     hipLaunchKernelGGL(k_fill_i32, dim3(fill_blocks), dim3(256), 0, s->stream, d_rc,
                        (long long)n_in, 0);
+    if (d_len)
+        hipLaunchKernelGGL(k_fill_i32, dim3(fill_blocks), dim3(256), 0, s->stream, d_len,
+                           (long long)n_in, n);
     if (s->n_items > 0) {
-        Items items{s->d_item_steps, s->d_item_base, s->d_item_len, s->d_item_pairs,
-                    s->d_item_pbase, s->n_items, s->d_item_common, s->d_item_hdr, s->d_item_weight};
-        if (dp_rows_fit_lds(s->max_aln_len))
-            hipLaunchKernelGGL(k_pairs<true>, dim3(DP_BLOCKS), dim3(DP_THREADS),
-                               dp_lds_bytes(s->max_aln_len), s->stream, items,
-                               s->d_slot_orig, s->d_images, L, s->d_rows, d_fw, d_rc);
+        const Items items = scorer_items(s);
+        const bool lds = dp_rows_fit_lds(s->max_aln_len);
+        const size_t lds_bytes = lds ? dp_lds_bytes(s->max_aln_len) : 0;
+        if (lds && d_len)
+            hipLaunchKernelGGL((k_pairs<true, true>), dim3(DP_BLOCKS), dim3(DP_THREADS), lds_bytes,
+                               s->stream, items, s->d_slot_orig, s->d_images, L, s->d_rows, d_fw, d_rc,
+                               d_len);
+        else if (lds)
+            hipLaunchKernelGGL((k_pairs<true, false>), dim3(DP_BLOCKS), dim3(DP_THREADS), lds_bytes,
+                               s->stream, items, s->d_slot_orig, s->d_images, L, s->d_rows, d_fw, d_rc,
+                               d_len);
+        else if (d_len)
+            hipLaunchKernelGGL((k_pairs<false, true>), dim3(DP_BLOCKS), dim3(DP_THREADS), 0,
+                               s->stream, items, s->d_slot_orig, s->d_images, L, s->d_rows, d_fw, d_rc,
+                               d_len);
         else
-            hipLaunchKernelGGL(k_pairs<false>, dim3(DP_BLOCKS), dim3(DP_THREADS), 0,
-                               s->stream, items, s->d_slot_orig, s->d_images, L,
-                               s->d_rows, d_fw, d_rc);
+            hipLaunchKernelGGL((k_pairs<false, false>), dim3(DP_BLOCKS), dim3(DP_THREADS), 0,
+                               s->stream, items, s->d_slot_orig, s->d_images, L, s->d_rows, d_fw, d_rc,
+                               d_len);
     }
-    std::vector<int32_t> h_fw(n_in), h_rc(n_in);
+    std::vector<int32_t> h_out((size_t)n_out * n_in);
     hipError_t e3 = hipGetLastError();
     if (e3 == hipSuccess)
-        e3 = hipMemcpyAsync(h_fw.data(), d_fw, n_in * sizeof(int32_t), hipMemcpyDeviceToHost,
-                            s->stream);
-    if (e3 == hipSuccess)
-        e3 = hipMemcpyAsync(h_rc.data(), d_rc, n_in * sizeof(int32_t), hipMemcpyDeviceToHost,
+        e3 = hipMemcpyAsync(h_out.data(), d_out, h_out.size() * sizeof(int32_t), hipMemcpyDeviceToHost,
                             s->stream);
     if (e3 == hipSuccess) e3 = hipStreamSynchronize(s->stream);
-    (void)hipFree(d_fw);
-    (void)hipFree(d_rc);
+    (void)hipFree(d_out);
     if (e3 != hipSuccess) {
         set_err("pair_scores: %s", hipGetErrorString(e3));
         return GFAL_E_HIP;
@@ -8027,12 +8210,164 @@ static int pair_scores_impl(gfal_scorer *s, const int32_t *path_steps, int32_t n
     for (size_t k = 0; k < n_in; ++k)
         if (s->owned[k]) {
             const size_t from = dedup ? (size_t)s->rep_of[k] : k;
-            fw[k] = h_fw[from];
-            rc_out[k] = h_rc[from];
+            fw[k] = h_out[from];
+            rc_out[k] = h_out[n_in + from];
+            if (ops_len) ops_len[k] = h_out[2 * n_in + from];
         }
     s->last_stream = s->stream;
     s->have_last = true;
     return gfal_scorer_sync_status(s);
+}
+
+// The lane of every caller alignment, and every item's length, from the device (once).
+static int trace_tables(gfal_scorer *s)
+{
+    if (!s->slot_of.empty() || s->n_aln_in == 0) return GFAL_OK;
+    const size_t n_slots = (size_t)s->n_items * WAVE;
+    std::vector<int32_t> slot_orig(n_slots);
+    std::vector<uint16_t> item_len((size_t)s->n_items);
+    if (n_slots) {
+        HIP_TRY(hipMemcpy(slot_orig.data(), s->d_slot_orig, n_slots * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(item_len.data(), s->d_item_len, item_len.size() * sizeof(uint16_t),
+                          hipMemcpyDeviceToHost));
+    }
+    std::vector<int32_t> slot_of((size_t)s->n_aln_in, -1);
+    for (size_t t = 0; t < n_slots; ++t)
+        if (slot_orig[t] >= 0) slot_of[(size_t)slot_orig[t]] = (int32_t)t;
+    s->slot_of.swap(slot_of);
+    s->h_item_len.swap(item_len);
+    return GFAL_OK;
+}
+
+// Move scratch of k_pair_ops in HBM: at most GFAL_TRACE_SCRATCH_MB (default 1024) MiB,
+// and never less than one wave's worth; the grid is the number of waves it holds.
+// A failed allocation halves the grid; GFAL_E_NOMEM only when one wave cannot have its own.
+static int trace_moves_reserve(gfal_scorer *s, size_t words_per_lane, int *grid)
+{
+    size_t budget = (size_t)1024 << 20;
+    if (const char *env = getenv("GFAL_TRACE_SCRATCH_MB")) budget = (size_t)std::max(1, atoi(env)) << 20;
+    const size_t wave_bytes = words_per_lane * DP_THREADS * sizeof(uint32_t);
+    int g = (int)std::min<size_t>((size_t)*grid, std::max<size_t>(1, budget / wave_bytes));
+    for (;; g /= 2) {
+        const size_t want = (size_t)g * DP_THREADS * words_per_lane;
+        if (want <= s->trace_moves_cap && s->d_trace_moves) break;
+        if (s->d_trace_moves) HIP_TRY(hipFree(s->d_trace_moves));
+        s->d_trace_moves = nullptr;
+        s->trace_moves_cap = 0;
+        if (hipMalloc(reinterpret_cast<void **>(&s->d_trace_moves), want * sizeof(uint32_t)) == hipSuccess) {
+            s->trace_moves_cap = want;
+            break;
+        }
+        (void)hipGetLastError();
+        if (g == 1) {
+            set_err("pair_alignment_ops: no room for the traceback scratch of one wave (%zu bytes)", wave_bytes);
+            return GFAL_E_NOMEM;
+        }
+    }
+    *grid = g;
+    return GFAL_OK;
+}
+
+static int pair_ops_impl(gfal_scorer *s, const int32_t *path_steps, int32_t n, int64_t k0,
+                         int64_t k1, const int64_t *ops_off, uint8_t *ops)
+{
+    if (!s || !path_steps) return GFAL_E_ARG;
+    if (k0 < 0 || k1 < k0 || k1 > s->n_aln_in) return GFAL_E_ARG;
+    if (k1 > k0 && (!ops_off || !ops)) return GFAL_E_ARG;
+    for (int64_t k = k0; k < k1; ++k)
+        if (ops_off[k - k0] < 0 || ops_off[k - k0 + 1] < ops_off[k - k0]) return GFAL_E_ARG;
+    ImageLayout L;
+    int rc = pair_prep(s, path_steps, n, &L);
+    if (rc != GFAL_OK || s->n_aln == 0) return rc;
+    if ((rc = trace_tables(s))) return rc;
+
+    // the lanes this range needs (a copy of a dedup scorer takes its representative's
+    // lane), sorted by lane; zero-step alignments are n up-moves and need none
+    const bool dedup = !s->rep_of.empty();
+    std::vector<TraceEntry> ent;
+    std::vector<int64_t> ent_k;            // the caller's alignment of each entry
+    std::vector<std::pair<int32_t, int64_t>> order;
+    for (int64_t k = k0; k < k1; ++k) {
+        if (!s->owned[(size_t)k]) continue;
+        const int64_t cap = ops_off[k - k0 + 1] - ops_off[k - k0];
+        const int32_t slot = s->slot_of[(size_t)(dedup ? s->rep_of[(size_t)k] : k)];
+        if (slot < 0) {
+            if (cap != n) {
+                set_err("pair_alignment_ops: alignment %lld has %d ops, not %lld", (long long)k, n,
+                        (long long)cap);
+                return GFAL_E_ARG;
+            }
+            memset(ops + ops_off[k - k0], 2, (size_t)n);
+            continue;
+        }
+        if (cap > 2 * GFAL_MAX_STEPS) {
+            set_err("pair_alignment_ops: alignment %lld given %lld ops", (long long)k, (long long)cap);
+            return GFAL_E_ARG;
+        }
+        order.emplace_back(slot, k);
+    }
+    std::sort(order.begin(), order.end());
+    ent.reserve(order.size());
+    ent_k.reserve(order.size());
+    long long total = 0;
+    int max_m = 0;
+    for (auto &o : order) {
+        const int32_t cap = (int32_t)(ops_off[o.second - k0 + 1] - ops_off[o.second - k0]);
+        ent.push_back(TraceEntry{total, o.first, cap});
+        ent_k.push_back(o.second);
+        total += cap;
+        max_m = std::max(max_m, (int)s->h_item_len[(size_t)(o.first >> 6)]);
+    }
+    if (ent.empty()) return gfal_scorer_sync_status(s);
+
+    if ((rc = dev_reserve(&s->d_trace_ent, &s->trace_ent_cap, ent.size()))) return rc;
+    // [uint32 bad count | ops]
+    if ((rc = dev_reserve(&s->d_trace_ops, &s->trace_ops_cap, (size_t)total + 4))) return rc;
+    HIP_TRY(hipMemcpyAsync(s->d_trace_ent, ent.data(), ent.size() * sizeof(TraceEntry), hipMemcpyHostToDevice,
+                           s->stream));
+    HIP_TRY(hipMemsetAsync(s->d_trace_ops, 0, 4, s->stream));
+    uint32_t *d_bad = reinterpret_cast<uint32_t *>(s->d_trace_ops);
+    uint8_t *d_ops = s->d_trace_ops + 4;
+
+    const int wpr = (max_m + 15) / 16;
+    const size_t move_words = (size_t)n * wpr;      // per lane
+    const bool rows_lds = dp_rows_fit_lds(s->max_aln_len);
+    const size_t row_bytes = rows_lds ? dp_lds_bytes(s->max_aln_len) : 0;
+    const size_t move_bytes = move_words * DP_THREADS * sizeof(uint32_t);
+    const bool moves_lds = rows_lds && row_bytes + move_bytes <= 48 * 1024;   // three waves per CU
+    int grid = (int)std::min<size_t>(DP_BLOCKS, (ent.size() + DP_THREADS - 1) / DP_THREADS);
+    if (!moves_lds && (rc = trace_moves_reserve(s, move_words, &grid))) return rc;
+    const Items items = scorer_items(s);
+    const int row_words = s->max_aln_len + 1;
+    if (moves_lds)
+        hipLaunchKernelGGL((k_pair_ops<true, true>), dim3(grid), dim3(DP_THREADS), row_bytes + move_bytes,
+                           s->stream, items, s->d_images, L, s->d_trace_ent, (int)ent.size(), row_words,
+                           s->d_rows, s->d_trace_moves, d_ops, d_bad);
+    else if (rows_lds)
+        hipLaunchKernelGGL((k_pair_ops<true, false>), dim3(grid), dim3(DP_THREADS), row_bytes, s->stream,
+                           items, s->d_images, L, s->d_trace_ent, (int)ent.size(), row_words, s->d_rows,
+                           s->d_trace_moves, d_ops, d_bad);
+    else
+        hipLaunchKernelGGL((k_pair_ops<false, false>), dim3(grid), dim3(DP_THREADS), 0, s->stream, items,
+                           s->d_images, L, s->d_trace_ent, (int)ent.size(), row_words, s->d_rows,
+                           s->d_trace_moves, d_ops, d_bad);
+    HIP_TRY(hipGetLastError());
+    std::vector<uint8_t> h_ops((size_t)total + 4);
+    HIP_TRY(hipMemcpyAsync(h_ops.data(), s->d_trace_ops, h_ops.size(), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    s->last_stream = s->stream;
+    s->have_last = true;
+    if ((rc = gfal_scorer_sync_status(s))) return rc;
+    uint32_t bad;
+    memcpy(&bad, h_ops.data(), sizeof(bad));
+    if (bad) {
+        set_err("pair_alignment_ops: %u alignments of the range have another op count than ops_off gives "
+                "(see gfal_scorer_pair_alignment_lengths)", bad);
+        return GFAL_E_ARG;
+    }
+    for (size_t e = 0; e < ent.size(); ++e)
+        memcpy(ops + ops_off[ent_k[e] - k0], h_ops.data() + 4 + ent[e].dst, (size_t)ent[e].cap);
+    return GFAL_OK;
 }
 
 int gfal_scorer_get_info(gfal_scorer *s, gfal_info *out)

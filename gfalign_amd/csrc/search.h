@@ -323,6 +323,38 @@ public:
         }
         return true;
     }
+    // fw / rc and the op count of every alignment's printed traceback (the winning
+    // orientation), in input order
+    bool pair_alignment_lengths(const std::vector<int32_t> &path, std::vector<int32_t> &fw,
+                                std::vector<int32_t> &rc, std::vector<int32_t> &ops_len)
+    {
+        fw.assign((size_t)n_aln_, 0);
+        rc.assign((size_t)n_aln_, 0);
+        ops_len.assign((size_t)n_aln_, 0);
+        for (gfal_scorer *h : shards_) {   // every shard writes the entries of its own alignments
+            int err = gfal_scorer_pair_alignment_lengths(h, path.data(), (int32_t)path.size(), fw.data(),
+                                                         rc.data(), ops_len.data());
+            if (err != GFAL_OK) {
+                fprintf(stderr, "Error: scorer: %s (%s)\n", gfal_strerror(err), gfal_last_error());
+                return false;
+            }
+        }
+        return true;
+    }
+    // the ops of alignments [k0, k1): alignment k's at ops[off[k-k0] .. off[k-k0+1])
+    bool pair_alignment_ops(const std::vector<int32_t> &path, int64_t k0, int64_t k1,
+                            const std::vector<int64_t> &off, std::vector<uint8_t> &ops)
+    {
+        for (gfal_scorer *h : shards_) {
+            int err = gfal_scorer_pair_alignment_ops(h, path.data(), (int32_t)path.size(), k0, k1, off.data(),
+                                                     ops.data());
+            if (err != GFAL_OK) {
+                fprintf(stderr, "Error: scorer: %s (%s)\n", gfal_strerror(err), gfal_last_error());
+                return false;
+            }
+        }
+        return true;
+    }
     int64_t n_aln() const { return n_aln_; }
     size_t n_shards() const { return shards_.size(); }
 

@@ -76,6 +76,12 @@ EXPORTS = {
     "gfal_scorer_sync_status": (ctypes.c_int, [ctypes.c_void_p]),
     "gfal_scorer_pair_scores": (ctypes.c_int, [ctypes.c_void_p, _i32p, ctypes.c_int32,
                                                _i32p, _i32p]),
+    "gfal_scorer_pair_alignment_lengths": (ctypes.c_int, [ctypes.c_void_p, _i32p, ctypes.c_int32,
+                                                          _i32p, _i32p, _i32p]),
+    "gfal_scorer_pair_alignment_ops": (ctypes.c_int, [ctypes.c_void_p, _i32p, ctypes.c_int32,
+                                                      ctypes.c_int64, ctypes.c_int64,
+                                                      ctypes.POINTER(ctypes.c_int64),
+                                                      ctypes.POINTER(ctypes.c_uint8)]),
     "gfal_scorer_set_profiling": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "gfal_scorer_get_info": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(GfalInfo)]),
 }
@@ -239,6 +245,57 @@ class Scorer:
             self._h, _ptr(path_steps, ctypes.c_int32), len(path_steps),
             _ptr(fw, ctypes.c_int32), _ptr(rc, ctypes.c_int32)))
         return fw, rc
+
+    def pair_alignment_lengths(self, path_steps, out=None):
+        """(fw, rc, ops_len): the scores of pair_scores and the op count of every
+        alignment's printed traceback (winning orientation).  `out` as in pair_scores."""
+        path_steps = _i32(path_steps)
+        if out is None:
+            out = tuple(np.zeros(self.n_aln, np.int32) for _ in range(3))
+        fw, rc, ops_len = out
+        assert all(a.dtype == np.int32 and len(a) == self.n_aln for a in out)
+        _check(self._lib.gfal_scorer_pair_alignment_lengths(
+            self._h, _ptr(path_steps, ctypes.c_int32), len(path_steps),
+            _ptr(fw, ctypes.c_int32), _ptr(rc, ctypes.c_int32), _ptr(ops_len, ctypes.c_int32)))
+        return fw, rc, ops_len
+
+    def pair_alignment_ops(self, path_steps, ops_off, ops, k0=0, k1=None):
+        """Write the ops of alignments [k0, k1) this scorer owns into `ops` (uint8) at
+        ops[ops_off[k]:ops_off[k + 1]]; ops_off (int64) comes from the op counts."""
+        path_steps = _i32(path_steps)
+        k1 = self.n_aln if k1 is None else k1
+        assert ops_off.dtype == np.int64 and ops.dtype == np.uint8 and ops.flags.c_contiguous
+        assert 0 <= k0 <= k1 <= self.n_aln and len(ops_off) == self.n_aln + 1
+        off = np.ascontiguousarray(ops_off[k0:k1 + 1])
+        _check(self._lib.gfal_scorer_pair_alignment_ops(
+            self._h, _ptr(path_steps, ctypes.c_int32), len(path_steps), int(k0), int(k1),
+            _ptr(off, ctypes.c_int64), _ptr(ops, ctypes.c_uint8)))
+
+    def pair_alignments(self, path_steps, out=None):
+        """What evalPath prints per alignment: (fw, rc, ops_off, ops), where
+        ops[ops_off[k]:ops_off[k + 1]] is alignment k's traceback of the winning
+        orientation (rc unless fw > rc), one op per column: 0 diagonal with equal
+        steps, 1 diagonal with different ones, 2 up (gap in the alignment's row),
+        3 left (gap in the path's row).  A shard fills its own alignments: pass the
+        result of the same call on the other shards of the set as `out` to fill one
+        result between them."""
+        n = self.n_aln
+        if out is None:
+            fw, rc = np.zeros(n, np.int32), np.zeros(n, np.int32)
+            old_off, old_ops = np.zeros(n + 1, np.int64), np.zeros(0, np.uint8)
+        else:
+            fw, rc, old_off, old_ops = out
+        old_len = np.diff(old_off).astype(np.int32)
+        ops_len = old_len.copy()
+        self.pair_alignment_lengths(path_steps, out=(fw, rc, ops_len))
+        ops_off = np.zeros(n + 1, np.int64)
+        np.cumsum(ops_len, out=ops_off[1:])
+        ops = np.zeros(int(ops_off[-1]), np.uint8)
+        if len(old_ops):   # what the other shards wrote moves with its alignment's offset
+            owner = np.repeat(np.arange(n), old_len)
+            ops[np.arange(len(old_ops)) - old_off[owner] + ops_off[owner]] = old_ops
+        self.pair_alignment_ops(path_steps, ops_off, ops)
+        return fw, rc, ops_off, ops
 
     def set_profiling(self, on=True):
         """True / 1: events around every phase of a call; 2: around the dominant scan

@@ -259,6 +259,36 @@ int gfal_scorer_sync_status(gfal_scorer *s);
 int gfal_scorer_pair_scores(gfal_scorer *s, const int32_t *path_steps, int32_t n,
                             int32_t *fw, int32_t *rc);
 
+/*
+ * The alignment evalPath prints (src/eval.cpp:100-102 with printAlignments): the
+ * traceback (src/alignments.cpp:511-554) of the winning orientation -- rc unless
+ * fw > rc -- as one op per column of the gapped rows, first column first:
+ *     0  diagonal, the two steps equal       row_a: path step   row_b: alignment step
+ *     1  diagonal, the two steps differ      row_a: path step   row_b: alignment step
+ *     2  up (also the free moves down column 0)      path step / gap
+ *     3  left (also the free moves along row 0)      gap / alignment step
+ * The oriented alignment is the stored one for fw and its reverse complement
+ * (include/alignments.h:64-70) for rc.  A zero-step alignment is n up-moves.
+ * Two calls, so that a caller can stream millions of rows in blocks:
+ *
+ * _lengths: fw, rc as gfal_scorer_pair_scores, and ops_len [n_aln given to create]
+ *   the op count of every alignment's traceback.  A shard writes the entries of its
+ *   own alignments only.
+ * _ops: the ops of alignments [k0, k1) of the caller's numbering.  ops_off holds
+ *   k1 - k0 + 1 offsets: alignment k's ops go to ops[ops_off[k-k0] .. ops_off[k-k0+1]),
+ *   a range that must be exactly ops_len[k] long (GFAL_E_ARG otherwise; nothing is
+ *   written outside it).  A shard writes the alignments it owns, a copy of a
+ *   gfal_scorer_create_dedup scorer gets its representative's ops.
+ *   GFAL_TRACE_SCRATCH_MB (default 1024) bounds the device scratch of long
+ *   alignments (n * m / 4 bytes each); it shrinks on allocation failure and the call
+ *   fails with GFAL_E_NOMEM only when 64 alignments' worth cannot be had.
+ * Arguments are checked as for gfal_scorer_pair_scores.
+ */
+int gfal_scorer_pair_alignment_lengths(gfal_scorer *s, const int32_t *path_steps, int32_t n,
+                                       int32_t *fw, int32_t *rc, int32_t *ops_len);
+int gfal_scorer_pair_alignment_ops(gfal_scorer *s, const int32_t *path_steps, int32_t n,
+                                   int64_t k0, int64_t k1, const int64_t *ops_off, uint8_t *ops);
+
 /* ---- introspection used by bench.py / tests; no effect on results ---- */
 
 typedef struct {
