@@ -37,10 +37,10 @@ const char *VERSION = "0.0.1";   // reference src/main.cpp:49
 
 struct Options {
     int mode = -1;
-    std::string gfa, gaf, node_file, source, destination, path, out_file;
+    std::string gfa, gaf, node_file, source, destination, path, out_file, path_file, alignments_file;
     uint32_t max_steps = 100000, min_nodes = 0;
     int return_all_paths = 0, cmd_flag = 0, stats_flag = 0, sort_alignment = 0;
-    int terminal_alignments = 0;
+    int terminal_alignments = 0, filter = 0;
     int device = 0, n_devices = 1;
     unsigned threads = 0;            // -j: host threads of the file readers (0 = default)
 };
@@ -248,13 +248,14 @@ std::string b_row_from_ops(const std::vector<Step> &A, const std::vector<Step> &
     return s;
 }
 
-int run_eval_path(const Options &o, const Graph &g, const std::vector<GafRecord> &recs)
+// src/eval.cpp:203-227: split on ',' / ';', last char = orientation.  Prints the
+// reference's message and returns false on a path it cannot use.
+bool parse_path(const std::string &text, const Graph &g, std::vector<Step> &path)
 {
-    // src/eval.cpp:203-227: split on ',' / ';', last char = orientation
-    std::vector<Step> path;
+    path.clear();
     std::string comp;
     std::vector<std::string> comps;
-    for (char c : o.path) {
+    for (char c : text) {
         if (c == ',' || c == ';') {
             comps.push_back(comp);
             comp.clear();
@@ -267,25 +268,32 @@ int run_eval_path(const Options &o, const Graph &g, const std::vector<GafRecord>
         std::string c = comps[k];
         if (k == 0 && c.empty()) {
             fprintf(stderr, "Error: cannot handle starting gap. Terminating.\n");
-            return 1;
+            return false;
         }
         if (c.empty()) {   // the reference would index an empty string here (UB)
             fprintf(stderr, "Error: cannot find node (). Terminating.\n");
-            return 1;
+            return false;
         }
         char orient = c.back();
         c.pop_back();
         auto it = g.ids.find(c);
         if (it == g.ids.end()) {
             fprintf(stderr, "Error: cannot find node (%s). Terminating.\n", c.c_str());
-            return 1;
+            return false;
         }
         path.push_back({(int32_t)it->second, orient});
     }
     if (path.size() > GFAL_MAX_STEPS) {
         fprintf(stderr, "Error: path longer than %d steps.\n", GFAL_MAX_STEPS);
-        return 1;
+        return false;
     }
+    return true;
+}
+
+int run_eval_path(const Options &o, const Graph &g, const std::vector<GafRecord> &recs)
+{
+    std::vector<Step> path;
+    if (!parse_path(o.path, g, path)) return 1;
     const uint32_t uniques = count_uniques(path);
 
     PackedAlignments packed;
@@ -452,6 +460,144 @@ int run_eval_path(const Options &o, const Graph &g, const std::vector<GafRecord>
     return 0;
 }
 
+// --------------------------------------------------------- comparePaths ---
+// The paths of a file (bare paths as evalPath -p takes them, or `search` output rows,
+// whose last tab field is the path) against every alignment: the counters of each
+// path, and for every pair of paths how many alignments are good for one and bad
+// for the other (gfal_scorer_discordance).  --alignments FILE: one row per alignment
+// whose verdicts differ between the paths, G / B / U per path
+// (gfal_scorer_verdicts).  The column sums of the verdicts must equal the counters.
+int run_compare_paths(const Options &o, const Graph &g, const std::vector<GafRecord> &recs)
+{
+    if (o.path_file.empty()) {
+        fprintf(stderr, "Error: comparePaths needs a path file (-P).\n");
+        return 1;
+    }
+    std::ifstream pf(o.path_file);
+    if (!pf) {
+        fprintf(stderr, "Error: cannot read %s\n", o.path_file.c_str());
+        return 1;
+    }
+    std::vector<std::string> given;          // each path as the file gives it
+    std::vector<int32_t> off{0}, pst, universe;
+    std::string line;
+    while (std::getline(pf, line)) {
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        if (line.empty() || line[0] == '#' || line.compare(0, 31, "Reached maximum number of steps") == 0)
+            continue;
+        const size_t tab = line.rfind('\t');
+        const std::string text = tab == std::string::npos ? line : line.substr(tab + 1);
+        std::vector<Step> path;
+        if (!parse_path(text, g, path)) return 1;
+        for (auto &st : path) {
+            pst.push_back(pack(st));
+            universe.push_back(st.id);
+        }
+        off.push_back((int32_t)pst.size());
+        given.push_back(text);
+    }
+    const size_t P = given.size();
+    if (P == 0) {
+        fprintf(stderr, "Error: no paths in %s\n", o.path_file.c_str());
+        return 1;
+    }
+    if (P > GFAL_MAX_COMPARE) {
+        fprintf(stderr, "Error: %zu paths; comparePaths takes at most %d.\n", P, GFAL_MAX_COMPARE);
+        return 1;
+    }
+    std::sort(universe.begin(), universe.end());
+    universe.erase(std::unique(universe.begin(), universe.end()), universe.end());
+
+    PackedAlignments packed;
+    for (auto &r : recs) packed.add(r, g);
+    PathScorer scorer;
+    const bool share = getenv("GFALIGN_SHARE_DEVICE") != nullptr;
+    if (!scorer.open(packed, (int32_t)g.headers.size(), o.device, universe, o.n_devices, share)) return 1;
+    const bool filter = o.filter != 0;
+    const int64_t n_aln = packed.size();
+    std::vector<uint32_t> bad(P, 0), good(P, 0), d(P * P, 0);
+    if (n_aln > 0) {       // (no alignments: every counter 0, no device needed)
+        if (!scorer.score(off, pst, filter, bad, good)) return 1;
+        if (!scorer.discordance(off, pst, filter, d)) return 1;
+    }
+    // the verdicts, a block of alignments at a time (GFALIGN_COMPARE_BLOCK alignments;
+    // default 1 GB of codes).  The lanes of a block in GAF order are spread over all of
+    // the scorer's items, so every block is a pass of the pipeline over the whole set:
+    // large blocks keep the passes few (config 3 at 1 024 paths: one; 10 M alignments
+    // x 1 024 paths: ten)
+    int64_t block = std::max<int64_t>(1, ((int64_t)1 << 30) / (int64_t)P);
+    if (const char *env = getenv("GFALIGN_COMPARE_BLOCK")) block = std::max<int64_t>(1, atoll(env));
+    std::ofstream aout;
+    if (!o.alignments_file.empty()) {
+        aout.open(o.alignments_file);
+        if (!aout) {
+            fprintf(stderr, "Error: cannot write %s\n", o.alignments_file.c_str());
+            return 1;
+        }
+    }
+    std::vector<uint64_t> sums(3 * P, 0);       // good | bad | unaligned per path
+    std::vector<uint8_t> codes;
+    std::string row;
+    for (int64_t k0 = 0; k0 < n_aln; k0 += block) {
+        const int64_t k1 = std::min(n_aln, k0 + block);
+        if (!scorer.verdicts(off, pst, filter, k0, k1, codes)) return 1;
+        for (int64_t k = k0; k < k1; ++k) {
+            const uint8_t *c = codes.data() + (size_t)(k - k0) * P;
+            bool same = true;
+            for (size_t p = 0; p < P; ++p) {
+                if (c[p] > 2) {
+                    fprintf(stderr, "Error: verdict %u of alignment %lld\n", (unsigned)c[p], (long long)k);
+                    return 1;
+                }
+                ++sums[(size_t)c[p] * P + p];
+                same &= c[p] == c[0];
+            }
+            if (aout.is_open() && !same) {
+                row.assign(recs[(size_t)k].qname);
+                row += '\t';
+                for (size_t p = 0; p < P; ++p) row += "GBU"[c[p]];
+                row += '\n';
+                aout.write(row.data(), (std::streamsize)row.size());
+            }
+        }
+    }
+    for (size_t p = 0; p < P; ++p) {
+        const uint64_t una = (uint64_t)n_aln - bad[p] - good[p];
+        if (sums[p] != good[p] || sums[P + p] != bad[p] || sums[2 * P + p] != una) {
+            fprintf(stderr,
+                    "Error: verdicts of path %zu (good %llu, bad %llu, unaligned %llu) disagree with its "
+                    "counters (good %u, bad %u, unaligned %llu)\n",
+                    p + 1, (unsigned long long)sums[p], (unsigned long long)sums[P + p],
+                    (unsigned long long)sums[2 * P + p], good[p], bad[p], (unsigned long long)una);
+            return 1;
+        }
+    }
+    if (aout.is_open()) {
+        aout.close();
+        if (!aout) {
+            fprintf(stderr, "Error: cannot write %s\n", o.alignments_file.c_str());
+            return 1;
+        }
+    }
+    std::string out = "#path\tbad\tgood\tunaligned\tpath\n";
+    for (size_t p = 0; p < P; ++p)
+        out += std::to_string(p + 1) + '\t' + std::to_string(bad[p]) + '\t' + std::to_string(good[p]) + '\t' +
+               std::to_string((uint64_t)n_aln - bad[p] - good[p]) + '\t' + given[p] + '\n';
+    out += "#pair\tgood_first_bad_second\tgood_second_bad_first\n";
+    for (size_t i = 0; i < P; ++i) {
+        for (size_t j = i + 1; j < P; ++j)
+            out += std::to_string(i + 1) + '\t' + std::to_string(j + 1) + '\t' + std::to_string(d[i * P + j]) +
+                   '\t' + std::to_string(d[j * P + i]) + '\n';
+        if (out.size() > (1u << 20)) {
+            std::cout << out;
+            out.clear();
+        }
+    }
+    std::cout << out;
+    std::cout.flush();
+    return std::cout ? 0 : 1;
+}
+
 // -------------------------------------------------------------- filter ---
 int run_filter(const Options &o, std::vector<GafRecord> &recs, const AlignmentTotals &totals)
 {
@@ -611,7 +757,7 @@ void print_help()
 {
     printf("gfalign [command]\n-h for additional help.\n");
     printf("\nModes:\n");
-    printf("evalGFA\nsearch\nfilter\nevalPath\n");
+    printf("evalGFA\nsearch\nfilter\nevalPath\ncomparePaths\n");
     exit(0);
 }
 
@@ -637,6 +783,7 @@ int main(int argc, char **argv)
     else if (tool == "search") o.mode = 3;
     else if (tool == "filter") o.mode = 4;
     else if (tool == "evalPath") o.mode = 5;
+    else if (tool == "comparePaths") o.mode = 6;
     else if (tool == "align" || tool == "subgraph") {
         fprintf(stderr, "mode '%s' is not part of this build (see DESIGN.md).\n", argv[1]);
         return EXIT_FAILURE;
@@ -668,13 +815,16 @@ int main(int argc, char **argv)
         {"min-nodes", required_argument, 0, 1},
         {"device", required_argument, 0, 2},
         {"devices", required_argument, 0, 3},
+        {"paths", required_argument, 0, 'P'},
+        {"alignments", required_argument, 0, 4},
+        {"filter", no_argument, &o.filter, 1},
         {"cmd", no_argument, &o.cmd_flag, 1},
         {"verbose", no_argument, &verbose_flag, 1},
         {"version", no_argument, 0, 'v'},
         {"help", no_argument, 0, 'h'},
         {0, 0, 0, 0}};
     int c, idx = 0;
-    while ((c = getopt_long(argc, argv, "-:d:f:g:j:m:n:o:p:s:vh", long_options, &idx)) != -1) {
+    while ((c = getopt_long(argc, argv, "-:d:f:g:j:m:n:o:p:P:s:vh", long_options, &idx)) != -1) {
         switch (c) {
         case 'd': o.destination = optarg; break;
         case 'f':
@@ -689,6 +839,8 @@ int main(int argc, char **argv)
         case 'n': require_file(optarg); o.node_file = optarg; break;
         case 'o': o.out_file = optarg; break;
         case 'p': o.path = optarg; break;
+        case 'P': require_file(optarg); o.path_file = optarg; break;
+        case 4: o.alignments_file = optarg; break;
         case 's': o.source = optarg; break;
         case 'j': o.threads = (unsigned)std::max(0, atoi(optarg)); break;   // main.cpp:472-474
         case 1: o.min_nodes = (uint32_t)atoi(optarg); break;
@@ -706,6 +858,12 @@ int main(int argc, char **argv)
             printf("-m --max-steps <int> limit graph exploration.\n");
             printf("-n --node-file <filename> list of nodes available to the search.\n");
             printf("-p --path path to evaluate (evalPath).\n");
+            printf("-P --paths <filename> paths to compare, one per line: a path as -p takes it, or a "
+                   "search output row (comparePaths).\n");
+            printf("--filter count only alignments whose nodes are all on the path, as search does "
+                   "(comparePaths; default: false).\n");
+            printf("--alignments <filename> write the verdicts (G / B / U per path) of every alignment "
+                   "whose verdicts differ (comparePaths).\n");
             printf("-s --source <string> source node.\n");
             printf("--return-all-paths return all viable paths as they are discovered, not only "
                    "better ones (default: false).\n");
@@ -736,7 +894,7 @@ int main(int argc, char **argv)
     }
     // HIP start-up (~0.2 s) runs beside the file parsing
     std::thread warm;
-    if (o.mode == 3 || o.mode == 5)
+    if (o.mode == 3 || o.mode == 5 || o.mode == 6)
         warm = std::thread([dev = o.device] {
             // an empty scorer brings up the runtime AND the device context
             if (gfal_device_count() <= dev) return;
@@ -836,6 +994,7 @@ int main(int argc, char **argv)
     }
     case 4: return run_filter(o, recs, totals);
     case 5: return run_eval_path(o, g, recs);
+    case 6: return run_compare_paths(o, g, recs);
     }
     return EXIT_SUCCESS;
 }

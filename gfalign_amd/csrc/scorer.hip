@@ -59,6 +59,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <exception>
+#include <functional>
 #include <memory>
 #include <new>
 #include <thread>
@@ -494,7 +495,21 @@ struct ScanArgs {
     uint32_t wl_capacity;
     uint32_t *wl_hist;        // [N_CLASSES * n_paths] entries per (length class, path)
     uint32_t *status;
+    // verdict sink (k_scan<W, true> only): good plane [n_paths][plane_items] then bad
+    // plane, one 64-bit word per (path slot, item of the slab [item_lo, items.n_items))
+    unsigned long long *planes;
+    uint32_t plane_items;
 };
+
+// Where the decisions of the scan and the exact DP go: the per-path counters (the
+// product instantiation, V = false) or -- V = true, gfal_scorer_verdicts and
+// gfal_scorer_discordance -- one good and one bad bit per (path slot, lane) of a slab.
+__device__ __forceinline__ unsigned long long *verdict_word(unsigned long long *planes, uint32_t plane_items,
+                                                           int n_paths, bool bad, uint32_t path,
+                                                           uint32_t item_rel)
+{
+    return planes + ((size_t)(bad ? n_paths : 0) + path) * plane_items + item_rel;
+}
 
 // Worklist entry: bit 63 = rc orientation has an overhang, bit 62 = fw has one,
 // bits 32..61 = path, bits 0..31 = slot (item * 64 + lane).
@@ -684,6 +699,19 @@ struct WaveCounts {
     }
 };
 
+// Verdict sink of k_scan: the wave's two ballots are the (item, path) words of the
+// planes, written whole -- every (item, path) pair is decided by one wave, once; the
+// lanes the scan hands to the exact DP are in neither word and get their bit there.
+__device__ __forceinline__ void scan_verdict(const ScanArgs &a, const TileView &tv, int p, int lane,
+                                             uint32_t slot, lanemask good_m, lanemask bad_m)
+{
+    if (lane != 0) return;
+    const uint32_t rel = (slot >> 6) - (uint32_t)a.item_lo;
+    const uint32_t path = (uint32_t)(tv.path0 + p);
+    *verdict_word(a.planes, a.plane_items, a.n_paths, false, path, rel) = good_m;
+    *verdict_word(a.planes, a.plane_items, a.n_paths, true, path, rel) = bad_m;
+}
+
 // Occurrence-chain search (DESIGN.md "k_scan"): is B a contiguous subpath of
 // the path, or of its reverse complement?  `e` = chain head for B[0]'s node
 // (ENT_NONE on lanes that take no part).  Both directions are forward scans:
@@ -801,17 +829,18 @@ __device__ __forceinline__ lanemask subpath_search_long(const uint16_t *__restri
 // short alignments (MC = 0: run-time).
 // W: dedup scorer (lane weights `w`); a separate instantiation, so that the
 // plain kernel carries nothing for it.
-template <int K, int MC, bool W>
+template <int K, int MC, bool W, bool V>
 __device__ __forceinline__ void scan_item(const ScanArgs &a, const TileView &tv,
                                           const uint16_t *__restrict__ bp,
                                           const uint32_t *__restrict__ pp, int M_rt, int lane,
                                           uint32_t slot, WaveCounts &wc, uint32_t w)
 {
     // dedup: the item's lanes and their total weight, once per item
-    const lanemask all_m = W ? WAVE_MASK(bp[0] != STEP_INVALID) : 0ull;
-    const uint32_t w_all = W ? wave_weight(all_m, w, lane) : 0u;
+    const lanemask all_m = (W && !V) ? WAVE_MASK(bp[0] != STEP_INVALID) : 0ull;
+    const uint32_t w_all = (W && !V) ? wave_weight(all_m, w, lane) : 0u;
     auto count = [&](int p, lanemask good_m, lanemask bad_m) {
-        if (W) wc.add_weighted(p, lane, good_m, bad_m, w, all_m, w_all);
+        if (V) scan_verdict(a, tv, p, lane, slot, good_m, bad_m);
+        else if (W) wc.add_weighted(p, lane, good_m, bad_m, w, all_m, w_all);
         else wc.add(p, lane, good_m, bad_m);
     };
     const int M = MC ? MC : M_rt;
@@ -937,16 +966,17 @@ __device__ __forceinline__ void scan_item(const ScanArgs &a, const TileView &tv,
 }
 
 // Same decision for alignments too long for registers.
-template <bool W>
+template <bool W, bool V>
 __device__ __forceinline__ void scan_item_long(const ScanArgs &a, const TileView &tv,
                                                const uint16_t *__restrict__ bp, int M,
                                                int lane, uint32_t slot, WaveCounts &wc, uint32_t w)
 {
     // dedup: the item's lanes and their total weight, once per item
-    const lanemask all_m = W ? WAVE_MASK(bp[0] != STEP_INVALID) : 0ull;
-    const uint32_t w_all = W ? wave_weight(all_m, w, lane) : 0u;
+    const lanemask all_m = (W && !V) ? WAVE_MASK(bp[0] != STEP_INVALID) : 0ull;
+    const uint32_t w_all = (W && !V) ? wave_weight(all_m, w, lane) : 0u;
     auto count = [&](int p, lanemask good_m, lanemask bad_m) {
-        if (W) wc.add_weighted(p, lane, good_m, bad_m, w, all_m, w_all);
+        if (V) scan_verdict(a, tv, p, lane, slot, good_m, bad_m);
+        else if (W) wc.add_weighted(p, lane, good_m, bad_m, w, all_m, w_all);
         else wc.add(p, lane, good_m, bad_m);
     };
     const uint32_t first_step = bp[0];
@@ -1000,7 +1030,7 @@ __device__ __forceinline__ void scan_item_long(const ScanArgs &a, const TileView
     wc.item_done();
 }
 
-template <bool W>
+template <bool W, bool V>
 __global__ __launch_bounds__(SCAN_THREADS, 6) void k_scan(ScanArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) uint16_t lds[];
@@ -1093,15 +1123,15 @@ __global__ __launch_bounds__(SCAN_THREADS, 6) void k_scan(ScanArgs a)
         const uint16_t *bp = a.items.steps + (size_t)base_v * WAVE + lane;
         const uint32_t slot = (uint32_t)it * WAVE + lane;
         const uint32_t *pp = a.items.pairs + (size_t)pbase_v * WAVE + lane;
-        const uint32_t w = W ? a.items.weight[slot] : 1u;
+        const uint32_t w = (W && !V) ? a.items.weight[slot] : 1u;
         if (M > 2 * MAX_REG_K + 1) {
-            scan_item_long<W>(a, tv, bp, M, lane, slot, wc, w);
+            scan_item_long<W, V>(a, tv, bp, M, lane, slot, wc, w);
             continue;
         }
         switch (M) {
 #define GFAL_CASE(MM)                                                          \
     case MM:                                                                   \
-        scan_item<MM / 2, MM, W>(a, tv, bp, pp, M, lane, slot, wc, w);         \
+        scan_item<MM / 2, MM, W, V>(a, tv, bp, pp, M, lane, slot, wc, w);      \
         break;
             GFAL_CASE(1) GFAL_CASE(2) GFAL_CASE(3) GFAL_CASE(4)
             GFAL_CASE(5) GFAL_CASE(6) GFAL_CASE(7) GFAL_CASE(8)
@@ -1111,9 +1141,9 @@ __global__ __launch_bounds__(SCAN_THREADS, 6) void k_scan(ScanArgs a)
 #define GFAL_CASE(KK)                                                          \
     case 2 * KK:                                                               \
     case 2 * KK + 1:                                                           \
-        scan_item<KK, 0, W>(a, tv, bp, pp, M, lane, slot, wc, w);              \
+        scan_item<KK, 0, W, V>(a, tv, bp, pp, M, lane, slot, wc, w);           \
         break;
-            case 17: scan_item<8, 0, W>(a, tv, bp, pp, M, lane, slot, wc, w); break;
+            case 17: scan_item<8, 0, W, V>(a, tv, bp, pp, M, lane, slot, wc, w); break;
             GFAL_CASE(9) GFAL_CASE(10) GFAL_CASE(11) GFAL_CASE(12)
             GFAL_CASE(13) GFAL_CASE(14) GFAL_CASE(15) GFAL_CASE(16)
 #undef GFAL_CASE
@@ -1121,6 +1151,7 @@ __global__ __launch_bounds__(SCAN_THREADS, 6) void k_scan(ScanArgs a)
         }   // items of this group of 64
     }
 
+    if (V) return;          // the planes hold everything
     // workgroup reduction through LDS (images are dead now), then one atomic
     // per counter per workgroup
     wc.flush();
@@ -2575,9 +2606,14 @@ struct DpArgs {
     uint32_t *bits;
     uint32_t bits_words;
     const int32_t *q_slot;      // image slot -> store slot or -1
+    // verdict sink (the <.., true> instantiations): see ScanArgs::planes
+    unsigned long long *planes;
+    uint32_t plane_items;
+    uint32_t plane_item_lo;
 };
 
 struct DpEntry {
+    uint32_t slot;  // item * 64 + lane
     uint32_t pos;
     uint32_t p;
     const uint16_t *astep, *bp;
@@ -2592,6 +2628,7 @@ __device__ __forceinline__ DpEntry load_entry(const DpArgs &a, uint32_t w, bool 
     DpEntry e;
     e.p = (uint32_t)(ent >> 32) & WL_PATH_MASK;
     const uint32_t slot = (uint32_t)ent;
+    e.slot = slot;
     const uint32_t it = slot >> 6, ln = slot & 63u;
     const uint16_t *img = a.images + (size_t)e.p * a.L.total;
     e.astep = img + a.L.step_at();
@@ -2626,9 +2663,17 @@ __device__ __forceinline__ bool wavefront_class(const DpArgs &a, uint32_t total,
 // path of the wave (runs of equal p; the list is sorted by path), not one per
 // lane -- all resident waves work on the same few paths at a time, and per-lane
 // atomics on those few words were 75 % of the DP phase.
+template <bool V = false>
 __device__ __forceinline__ void add_results_by_path(const DpArgs &a, uint32_t p, bool live,
-                                                    bool good, int lane, uint32_t w = 1u, uint32_t pos = 0u)
+                                                    bool good, int lane, uint32_t w = 1u, uint32_t pos = 0u,
+                                                    uint32_t slot = 0u)
 {
+    if (V) {     // verdict sink: the pair's bit in its (item, path) word
+        if (live)
+            atomicOr(verdict_word(a.planes, a.plane_items, a.n_paths, !good, p, (slot >> 6) - a.plane_item_lo),
+                     1ull << (slot & 63u));
+        return;
+    }
     if (a.bits != nullptr && live && good) {       // search mode: remembered for the path's children
         const int slot = a.q_slot[p];
         // (a path whose first node has a longer list than the bitmaps hold keeps none:
@@ -2664,7 +2709,7 @@ __device__ __forceinline__ void add_results_by_path(const DpArgs &a, uint32_t p,
 }
 
 // Length classes 0..3: rows in MC registers.
-template <int MC, int CLS>
+template <int MC, int CLS, bool V>
 __global__ __launch_bounds__(DP_THREADS) void k_dp_regs(DpArgs a)
 {
     __shared__ uint32_t rowbits[ROW_WORDS][DP_THREADS];   // per lane: rows whose node is in B
@@ -2729,7 +2774,7 @@ __global__ __launch_bounds__(DP_THREADS) void k_dp_regs(DpArgs a)
 #if defined(GFAL_ABLATE) && GFAL_ABLATE == 3
         good = false;
 #endif
-        add_results_by_path(a, e.p, live, good, lane, e.w, e.pos);
+        add_results_by_path<V>(a, e.p, live, good, lane, e.w, e.pos, e.slot);
     }
 }
 
@@ -2789,7 +2834,7 @@ struct DpSysLds {
 // block `block` of `n_blocks` of the wavefront DP over its length class.  whole (k_dp_small):
 // the list is short and NOT sorted -- every entry of it with min_m <= m <= MC is this
 // function's, wherever it sits
-template <int MC>
+template <int MC, bool V = false>
 __device__ __forceinline__ void dp_sys_body(const DpArgs &a, uint32_t block, uint32_t n_blocks,
                                             unsigned char *smem, bool whole, int min_m)
 {
@@ -2958,15 +3003,15 @@ __device__ __forceinline__ void dp_sys_body(const DpArgs &a, uint32_t block, uin
         const lanemask gm = WAVE_MASK(good);
         const lanemask mine = (gm >> (lane / SPAN * SPAN)) & (SPAN == 64 ? ~0ull : ((1ull << SPAN) - 1ull));
         // one result per entry, carried by the first lane of its span
-        add_results_by_path(a, e.p, live && lane % SPAN == 0, mine != 0, lane, e.w, e.pos);
+        add_results_by_path<V>(a, e.p, live && lane % SPAN == 0, mine != 0, lane, e.w, e.pos, e.slot);
     }
 }
 
-template <int MC>
+template <int MC, bool V>
 __global__ __launch_bounds__(DP_THREADS) void k_dp_sys(DpArgs a)
 {
     __shared__ __attribute__((aligned(16))) unsigned char smem[DpSysLds<MC>::BYTES];
-    dp_sys_body<MC>(a, blockIdx.x, gridDim.x, smem, false, 0);
+    dp_sys_body<MC, V>(a, blockIdx.x, gridDim.x, smem, false, 0);
 }
 
 // The search's batches leave the exact DP a few hundred to a few thousand pairs in all:
@@ -2998,7 +3043,7 @@ __global__ __launch_bounds__(DP_THREADS) void k_dp_small(DpArgs a)
 }
 
 // Last length class (more than 32 steps): rows in LDS or HBM.
-template <bool ROWS_IN_LDS>
+template <bool ROWS_IN_LDS, bool V>
 __global__ __launch_bounds__(DP_THREADS) void k_dp_long(DpArgs a)
 {
     int stride;
@@ -3022,7 +3067,7 @@ __global__ __launch_bounds__(DP_THREADS) void k_dp_long(DpArgs a)
         B.flip = 1u;
         const int rc = traceback_score(A, B, row, stride);
         const bool good = fw == 0 || rc == 0;
-        add_results_by_path(a, e.p, mine, good, (int)threadIdx.x, e.w, e.pos);
+        add_results_by_path<V>(a, e.p, mine, good, (int)threadIdx.x, e.w, e.pos, e.slot);
     }
 }
 
@@ -3157,6 +3202,136 @@ __global__ void k_fill_i32(int32_t *p, long long n, int32_t v)
 {
     long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) p[i] = v;
+}
+
+// --------------------------------------------------------------------------
+// Verdicts (gfal_scorer_verdicts / gfal_scorer_discordance).  k_scan<.., true> and
+// the DP kernels' <.., true> instantiations leave, per slab of items, two bit planes:
+// word [path slot][item] of the good plane has bit l set when lane l of the item is
+// good for the path, the bad plane likewise; a lane that fails the filter (or a
+// padding lane) is in neither.  The kernels below read them.
+// --------------------------------------------------------------------------
+
+// codes[e * n_paths + order[q]] for the lanes ent_slot[0 .. n_ent) of the slab (all of
+// them inside it) and every path slot q: 0 good, 1 bad, 2 unaligned.
+__global__ __launch_bounds__(256) void k_verdict_codes(const unsigned long long *__restrict__ planes,
+                                                       uint32_t plane_items, uint32_t item_lo, int n_paths,
+                                                       const int32_t *__restrict__ order,
+                                                       const uint32_t *__restrict__ ent_slot, uint32_t n_ent,
+                                                       uint8_t *__restrict__ codes)
+{
+    const long long total = (long long)n_ent * n_paths;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+         i += (long long)gridDim.x * blockDim.x) {
+        const uint32_t e = (uint32_t)(i / n_paths), q = (uint32_t)(i % n_paths);
+        const uint32_t slot = ent_slot[e];
+        const uint32_t rel = (slot >> 6) - item_lo, bit = slot & 63u;
+        const unsigned long long g = planes[(size_t)q * plane_items + rel];
+        const unsigned long long b = planes[((size_t)n_paths + q) * plane_items + rel];
+        codes[(size_t)e * n_paths + (uint32_t)order[q]] = ((g >> bit) & 1ull) ? 0 : ((b >> bit) & 1ull) ? 1 : 2;
+    }
+}
+
+// Dedup scorers: bit b of every lane weight as one word per item, wplanes[b][item of the
+// slab], so that k_discord can weigh a word of lanes by bit slices.
+__global__ __launch_bounds__(256) void k_weight_planes(const uint32_t *__restrict__ weight, uint32_t item_lo,
+                                                       uint32_t plane_items, int wbits,
+                                                       unsigned long long *__restrict__ wplanes)
+{
+    const uint32_t rel = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
+    const int lane = threadIdx.x & (WAVE - 1);
+    if (rel >= plane_items) return;          // wave-uniform
+    const uint32_t w = weight[((size_t)item_lo + rel) * WAVE + lane];
+    for (int b = 0; b < wbits; ++b) {
+        const unsigned long long m = __builtin_amdgcn_ballot_w64(((w >> b) & 1u) != 0u);
+        if (lane == 0) wplanes[(size_t)b * plane_items + rel] = m;
+    }
+}
+
+// d[order[i] * n_paths + order[j]] += sum over the slab's lanes of w * (good for path slot
+// i AND bad for path slot j): the caller's path numbering, through the slot order of the
+// pass that made these planes (every slab's pass sorts the paths again, and paths of
+// equal length may come out in another order).  A workgroup owns a DISC_T x DISC_T tile of (i, j) and the item
+// words [blockIdx.z * words_per_group, +words_per_group); each round stages DISC_WORDS
+// words of the tile's 64 good rows and 64 bad rows in LDS, and every thread keeps
+// 4 x 4 pairs i = i0 + ti + 16 a, j = j0 + tj + 16 b in registers: per word and pair
+// one 64-bit AND and one 64-bit popcount (two v_and_b32, two v_bcnt_u32_b32), the
+// 8 LDS reads per word shared by 16 pairs.  Reads of the bad rows are 16 consecutive
+// words per lane group (no bank conflict), of the good rows 4 broadcast addresses; the
+// row pitch of 65 words keeps the staging stores (16 lanes, consecutive item words of
+// one row) apart.  W (dedup): the AND is weighed bit slice by bit slice.
+constexpr int DISC_T = 64;
+constexpr int DISC_WORDS = 32;
+constexpr int DISC_THREADS = 256;
+constexpr int DISC_MAX_WBITS = 32;
+
+template <bool W>
+__global__ __launch_bounds__(DISC_THREADS) void k_discord(const unsigned long long *__restrict__ planes,
+                                                          uint32_t plane_items, int n_paths,
+                                                          const unsigned long long *__restrict__ wplanes,
+                                                          int wbits, uint32_t words_per_group,
+                                                          const int32_t *__restrict__ order,
+                                                          uint32_t *__restrict__ d)
+{
+    __shared__ unsigned long long g_s[DISC_WORDS][DISC_T + 1], b_s[DISC_WORDS][DISC_T + 1];
+    __shared__ unsigned long long w_s[W ? DISC_WORDS : 1][W ? DISC_MAX_WBITS : 1];
+    const int tid = threadIdx.x;
+    const int ti = tid >> 4, tj = tid & 15;
+    const int i0 = blockIdx.x * DISC_T, j0 = blockIdx.y * DISC_T;
+    const uint32_t t_begin = blockIdx.z * words_per_group;
+    const uint32_t t_end = min(plane_items, t_begin + words_per_group);
+    uint32_t acc[4][4];
+#pragma unroll
+    for (int x = 0; x < 4; ++x)
+#pragma unroll
+        for (int y = 0; y < 4; ++y) acc[x][y] = 0;
+    for (uint32_t t0 = t_begin; t0 < t_end; t0 += DISC_WORDS) {
+        __syncthreads();
+        for (int k = tid; k < DISC_WORDS * DISC_T; k += DISC_THREADS) {
+            const int r = k / DISC_WORDS, c = k % DISC_WORDS;     // consecutive item words of one row
+            const uint32_t t = t0 + (uint32_t)c;
+            const bool in = t < t_end;
+            const int gi = i0 + r, bj = j0 + r;
+            g_s[c][r] = (in && gi < n_paths) ? planes[(size_t)gi * plane_items + t] : 0ull;
+            b_s[c][r] = (in && bj < n_paths) ? planes[((size_t)n_paths + bj) * plane_items + t] : 0ull;
+        }
+        if (W)
+            for (int k = tid; k < DISC_WORDS * wbits; k += DISC_THREADS) {
+                const int c = k / wbits, bb = k % wbits;
+                const uint32_t t = t0 + (uint32_t)c;
+                w_s[c][bb] = t < t_end ? wplanes[(size_t)bb * plane_items + t] : 0ull;
+            }
+        __syncthreads();
+        const int n_c = (int)min((uint32_t)DISC_WORDS, t_end - t0);
+        for (int c = 0; c < n_c; ++c) {
+            unsigned long long g[4], b[4];
+#pragma unroll
+            for (int x = 0; x < 4; ++x) {
+                g[x] = g_s[c][ti + 16 * x];
+                b[x] = b_s[c][tj + 16 * x];
+            }
+#pragma unroll
+            for (int x = 0; x < 4; ++x)
+#pragma unroll
+                for (int y = 0; y < 4; ++y) {
+                    const unsigned long long v = g[x] & b[y];
+                    if (W) {
+                        for (int bb = 0; bb < wbits; ++bb)
+                            acc[x][y] += (uint32_t)__popcll(v & w_s[c][bb]) << bb;
+                    } else {
+                        acc[x][y] += (uint32_t)__popcll(v);
+                    }
+                }
+        }
+    }
+#pragma unroll
+    for (int x = 0; x < 4; ++x)
+#pragma unroll
+        for (int y = 0; y < 4; ++y) {
+            const int i = i0 + ti + 16 * x, j = j0 + tj + 16 * y;
+            if (i < n_paths && j < n_paths && acc[x][y] != 0u)
+                atomicAdd(&d[(size_t)order[i] * n_paths + order[j]], acc[x][y]);
+        }
 }
 
 }  // namespace
@@ -5429,6 +5604,13 @@ struct gfal_scorer {
     uint8_t *d_trace_ops = nullptr;
     uint32_t *d_trace_moves = nullptr;
     size_t trace_ent_cap = 0, trace_ops_cap = 0, trace_moves_cap = 0;
+    // gfal_scorer_verdicts / _discordance: slab scratch (planes, codes, weight planes)
+    // and the result matrix; the largest lane weight (1 unless a dedup scorer)
+    unsigned char *d_verdict = nullptr;
+    size_t verdict_cap = 0;
+    uint32_t *d_discord = nullptr;
+    size_t discord_cap = 0;
+    uint32_t max_weight = 1;
     uint16_t *d_images = nullptr;
     size_t images_cap = 0;             // uint16 units
 
@@ -5552,7 +5734,7 @@ void free_scorer(gfal_scorer *s)
                     s->d_ct_hash,    s->d_ct_mult,   s->d_pair_bits, s->d_st_steps,   s->d_st_len,
                     s->d_st_pass,    s->d_st_g1,     s->d_child_in,   s->d_child_tmp,
                     s->d_st_bits,    s->d_st_bitsok, s->d_wl_pos,     s->d_wl_pos_sorted,
-                    s->d_trace_ent,  s->d_trace_ops, s->d_trace_moves};
+                    s->d_trace_ent,  s->d_trace_ops, s->d_trace_moves, s->d_verdict, s->d_discord};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (s->graph_exec) (void)hipGraphExecDestroy(s->graph_exec);
@@ -6315,10 +6497,13 @@ static int create_impl(const int32_t *aln_off, const int32_t *aln_steps, int64_t
         CREATE_TRY(hipEventCreateWithFlags(&s->dp_join[i], hipEventDisableTiming));
     }
     // both kernels may ask for more than the default 64 KiB of dynamic LDS
-    CREATE_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_scan<false>),
+    CREATE_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_scan<false, false>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize,
                                    LDS_BUDGET));
-    CREATE_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_scan<true>),
+    CREATE_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_scan<true, false>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   LDS_BUDGET));
+    CREATE_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_scan<false, true>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize,
                                    LDS_BUDGET));
     for (int w = 0; w < 2; ++w)
@@ -6345,6 +6530,7 @@ static int create_impl(const int32_t *aln_off, const int32_t *aln_steps, int64_t
     if ((rc = dev_upload(&s->d_item_pbase, item_pbase))) return fail(rc);
     if ((rc = dev_upload(&s->d_item_common, item_common))) return fail(rc);
     if (dedup && (rc = dev_upload(&s->d_item_weight, item_weight))) return fail(rc);
+    if (dedup && !item_weight.empty()) s->max_weight = std::max(1u, *std::max_element(item_weight.begin(), item_weight.end()));
     if ((rc = dev_upload(&s->d_item_hash, item_hash))) return fail(rc);
     if ((rc = dev_upload(&s->d_item_pairs0, item_pairs0))) return fail(rc);
     for (size_t it = 0; it < src.size(); ++it)
@@ -6682,10 +6868,13 @@ static int launch_scan3(gfal_scorer *s, hipStream_t st, const Items &items, cons
 
 // What a call does besides scoring (search mode, see k_child).
 struct ExtraCtx {
-    int mode = 0;                    // 1: keep the batch's paths in the store; 2: children batch
+    int mode = 0;                    // 1: keep the batch's paths in the store; 2: children batch;
+                                     // 3: verdicts of the items [item_lo, item_hi) into `planes`
     const int32_t *d_slots = nullptr;   // mode 1: [n_paths] store slot per path or -1
     uint32_t *d_g1_tmp = nullptr;       // mode 1: [n_paths] scratch
     ChildBatch batch;                // mode 2
+    unsigned long long *planes = nullptr;   // mode 3: see ScanArgs::planes (cleared by the caller)
+    int item_lo = 0, item_hi = 0;
 };
 
 static int score_device_impl(gfal_scorer *s, const int32_t *d_path_off,
@@ -6826,7 +7015,19 @@ static int score_device_impl(gfal_scorer *s, const int32_t *d_path_off,
         if (!hash_fits || s->scan_mode == 1) n_segs2 = 0;
         if (!chain_fits || s->scan_mode == 2 || s->scan_mode == 3) n_segs2 = (int)s->segs.size();
         if (n_segs2 == 0 && !chain_fits) return GFAL_E_RANGE;
-        const int item_lo_chain = n_segs2 > 0 ? (int)s->segs[(size_t)n_segs2 - 1].item_hi : 0;
+        // verdicts: k_scan over the slab whatever GFAL_SCAN says (k_scan2 / k_scan3 count
+        // through multiplicities and per-tile lists and have no per-lane decision to keep)
+        const bool verdict = cx && cx->mode == 3;
+        if (verdict) {
+            if (!chain_fits) {
+                set_err("%d local nodes and paths of up to %d steps exceed the LDS budget of k_scan, "
+                        "which the verdict calls need", s->n_local, (int)max_path_len);
+                return GFAL_E_RANGE;
+            }
+            n_segs2 = 0;
+        }
+        const int item_lo_chain = verdict ? cx->item_lo
+                                          : n_segs2 > 0 ? (int)s->segs[(size_t)n_segs2 - 1].item_hi : 0;
         if (children) {
             // every child from its parent: the two inverted lists and the content table
             // instead of a scan over all alignments
@@ -6975,6 +7176,7 @@ static int score_device_impl(gfal_scorer *s, const int32_t *d_path_off,
 
         ScanArgs a;
         a.items = items;
+        if (verdict) a.items.n_items = cx->item_hi;
         a.images = s->d_images;
         a.L = L;
         a.n_paths = n_paths;
@@ -6986,7 +7188,9 @@ static int score_device_impl(gfal_scorer *s, const int32_t *d_path_off,
         a.wl_hist = d_hist;
         a.status = s->d_status;
         a.item_lo = item_lo_chain;
-        const int n_items_chain = s->n_items - item_lo_chain;
+        a.planes = verdict ? cx->planes : nullptr;
+        a.plane_items = verdict ? (uint32_t)(cx->item_hi - cx->item_lo) : 0u;
+        const int n_items_chain = a.items.n_items - item_lo_chain;
         if (n_items_chain > 0 && !children) {
             int tile = (int)std::min<size_t>(((size_t)LDS_BUDGET - mask_bytes) / img_bytes,
                                              MAX_TILE);
@@ -7018,10 +7222,12 @@ static int score_device_impl(gfal_scorer *s, const int32_t *d_path_off,
             const size_t lds = std::max((size_t)tile * img_bytes + mask_bytes,
                                         (size_t)2 * MAX_TILE * sizeof(uint32_t));
             const unsigned grid = (unsigned)a.n_tiles * (unsigned)a.n_chunks;
-            if (s->d_item_weight)
-                hipLaunchKernelGGL(k_scan<true>, dim3(grid), dim3(SCAN_THREADS), lds, st, a);
+            if (verdict)           // (weights are the discordance kernel's business)
+                hipLaunchKernelGGL((k_scan<false, true>), dim3(grid), dim3(SCAN_THREADS), lds, st, a);
+            else if (s->d_item_weight)
+                hipLaunchKernelGGL((k_scan<true, false>), dim3(grid), dim3(SCAN_THREADS), lds, st, a);
             else
-                hipLaunchKernelGGL(k_scan<false>, dim3(grid), dim3(SCAN_THREADS), lds, st, a);
+                hipLaunchKernelGGL((k_scan<false, false>), dim3(grid), dim3(SCAN_THREADS), lds, st, a);
             HIP_TRY(hipGetLastError());
             if (n_segs2 == 0) {
                 s->last_tile = tile;
@@ -7069,6 +7275,9 @@ static int score_device_impl(gfal_scorer *s, const int32_t *d_path_off,
         d.bits = inherit ? s->d_st_bits : nullptr;
         d.bits_words = s->bits_words;
         d.q_slot = inherit ? cx->batch.slot : nullptr;
+        d.planes = a.planes;
+        d.plane_items = a.plane_items;
+        d.plane_item_lo = (uint32_t)a.item_lo;
         if (dp_small)
             hipLaunchKernelGGL(k_dp_small, dim3(512, 4), dim3(DP_THREADS), 0, st, d);
         // fork: classes 8 / 16 / 32+ on side streams, class 4 on the caller's
@@ -7081,43 +7290,47 @@ static int score_device_impl(gfal_scorer *s, const int32_t *d_path_off,
         };
         // every kernel of both families is launched; the list length (known on
         // the device only) decides which family returns at once
-        if (!dp_small) {
+        // (the verdict sink: the same launches of the <.., true> instantiations)
+        auto launch_dp = [&](auto sink) {
+        constexpr bool V = decltype(sink)::value;
         const bool big = n_paths >= 2048;
         // (a big batch: the throughput kernel first, here too -- the other family's workgroups
         // return at once, but a launch in front of the one with the work is 6-12 us of the step)
-        if (!big) hipLaunchKernelGGL(k_dp_sys<4>, dim3(DP_SYS_BLOCKS), dim3(DP_THREADS), 0, st, d);
-        hipLaunchKernelGGL((k_dp_regs<4, 0>), dim3(DP_REG_BLOCKS), dim3(DP_THREADS), 0, st, d);
-        if (big) hipLaunchKernelGGL(k_dp_sys<4>, dim3(DP_SYS_BLOCKS), dim3(DP_THREADS), 0, st, d);
+        if (!big) hipLaunchKernelGGL((k_dp_sys<4, V>), dim3(DP_SYS_BLOCKS), dim3(DP_THREADS), 0, st, d);
+        hipLaunchKernelGGL((k_dp_regs<4, 0, V>), dim3(DP_REG_BLOCKS), dim3(DP_THREADS), 0, st, d);
+        if (big) hipLaunchKernelGGL((k_dp_sys<4, V>), dim3(DP_SYS_BLOCKS), dim3(DP_THREADS), 0, st, d);
         if (s->max_aln_len > 4) {
             hipStream_t s0 = side(0);
             // (a big batch: the throughput kernel first -- behind the other family's launch,
             // whose workgroups return at once but queue for CU slots behind k_dp_regs<4>'s, it
             // started 110 us late at config 3)
-            if (big) hipLaunchKernelGGL((k_dp_regs<8, 1>), dim3(DP_REG_BLOCKS), dim3(DP_THREADS), 0, s0, d);
-            hipLaunchKernelGGL(k_dp_sys<8>, dim3(DP_SYS_BLOCKS), dim3(DP_THREADS), 0, s0, d);
-            if (!big) hipLaunchKernelGGL((k_dp_regs<8, 1>), dim3(DP_REG_BLOCKS), dim3(DP_THREADS), 0, s0, d);
+            if (big) hipLaunchKernelGGL((k_dp_regs<8, 1, V>), dim3(DP_REG_BLOCKS), dim3(DP_THREADS), 0, s0, d);
+            hipLaunchKernelGGL((k_dp_sys<8, V>), dim3(DP_SYS_BLOCKS), dim3(DP_THREADS), 0, s0, d);
+            if (!big) hipLaunchKernelGGL((k_dp_regs<8, 1, V>), dim3(DP_REG_BLOCKS), dim3(DP_THREADS), 0, s0, d);
         }
         if (s->max_aln_len > 8) {
             hipStream_t s1 = side(1);
             // up to 32 k entries, two per wave: enough blocks that none loops for long
-            if (big) hipLaunchKernelGGL((k_dp_regs<16, 2>), dim3(DP_REG_BLOCKS), dim3(DP_THREADS), 0, s1, d);
-            hipLaunchKernelGGL(k_dp_sys<16>, dim3(4 * DP_SYS_BLOCKS), dim3(DP_THREADS), 0, s1, d);
-            if (!big) hipLaunchKernelGGL((k_dp_regs<16, 2>), dim3(DP_REG_BLOCKS), dim3(DP_THREADS), 0, s1, d);
+            if (big) hipLaunchKernelGGL((k_dp_regs<16, 2, V>), dim3(DP_REG_BLOCKS), dim3(DP_THREADS), 0, s1, d);
+            hipLaunchKernelGGL((k_dp_sys<16, V>), dim3(4 * DP_SYS_BLOCKS), dim3(DP_THREADS), 0, s1, d);
+            if (!big) hipLaunchKernelGGL((k_dp_regs<16, 2, V>), dim3(DP_REG_BLOCKS), dim3(DP_THREADS), 0, s1, d);
         }
         if (s->max_aln_len > 16) {
             hipStream_t s2 = side(2);
-            hipLaunchKernelGGL(k_dp_sys<64>, dim3(2 * DP_SYS_BLOCKS), dim3(DP_THREADS), 0, s2, d);
-            hipLaunchKernelGGL((k_dp_regs<32, 3>), dim3(DP_REG_BLOCKS), dim3(DP_THREADS), 0, s2, d);
+            hipLaunchKernelGGL((k_dp_sys<64, V>), dim3(2 * DP_SYS_BLOCKS), dim3(DP_THREADS), 0, s2, d);
+            hipLaunchKernelGGL((k_dp_regs<32, 3, V>), dim3(DP_REG_BLOCKS), dim3(DP_THREADS), 0, s2, d);
             if (s->max_aln_len > 32) {
                 if (dp_rows_fit_lds(s->max_aln_len))
-                    hipLaunchKernelGGL(k_dp_long<true>, dim3(DP_BLOCKS), dim3(DP_THREADS),
+                    hipLaunchKernelGGL((k_dp_long<true, V>), dim3(DP_BLOCKS), dim3(DP_THREADS),
                                        dp_lds_bytes(s->max_aln_len), s2, d);
                 else
-                    hipLaunchKernelGGL(k_dp_long<false>, dim3(DP_BLOCKS), dim3(DP_THREADS), 0,
+                    hipLaunchKernelGGL((k_dp_long<false, V>), dim3(DP_BLOCKS), dim3(DP_THREADS), 0,
                                        s2, d);
             }
         }
-        }
+        };
+        if (verdict) launch_dp(std::true_type());
+        else if (!dp_small) launch_dp(std::false_type());
         for (int i = 0; i < 3; ++i)        // join
             if (forked & (1 << i)) {
                 HIP_TRY(hipEventRecord(s->dp_join[i], s->dp_stream[i]));
@@ -8368,6 +8581,255 @@ static int pair_ops_impl(gfal_scorer *s, const int32_t *path_steps, int32_t n, i
     for (size_t e = 0; e < ent.size(); ++e)
         memcpy(ops + ops_off[ent_k[e] - k0], h_ops.data() + 4 + ent[e].dst, (size_t)ent[e].cap);
     return GFAL_OK;
+}
+
+// --------------------------------------------------------------------------
+// gfal_scorer_verdicts / gfal_scorer_discordance: the batch pipeline (k_prep, k_scan,
+// worklist sort, exact DP) with the verdict sink, over the resident items in slabs.
+// --------------------------------------------------------------------------
+static int check_batch(gfal_scorer *s, const int32_t *path_off, const int32_t *path_steps, int32_t n_paths,
+                       int32_t *max_len)
+{
+    if (!path_off || !path_steps || path_off[0] != 0) return GFAL_E_ARG;
+    *max_len = 1;
+    for (int32_t p = 0; p < n_paths; ++p) {
+        const int64_t n = (int64_t)path_off[p + 1] - path_off[p];
+        if (n < 1 || n > GFAL_MAX_STEPS) {
+            set_err("path %d has %lld steps (allowed 1..%d)", p, (long long)n, GFAL_MAX_STEPS);
+            return GFAL_E_RANGE;
+        }
+        *max_len = std::max(*max_len, (int32_t)n);
+    }
+    for (int64_t t = 0; t < path_off[n_paths]; ++t) {
+        const int32_t st = path_steps[t];
+        if (st < 0 || ((st & ~GFAL_STEP_OTHER) >> 1) >= s->n_nodes) {
+            set_err("path step %lld: node id out of range", (long long)t);
+            return GFAL_E_RANGE;
+        }
+    }
+    return GFAL_OK;
+}
+
+// Slab scratch: GFAL_VERDICT_SCRATCH_MB (default 1024, read at every call) bounds it;
+// `per_item` bytes per item of a slab.  A failed allocation halves the slab;
+// GFAL_E_NOMEM only when one item's worth cannot be had.
+static int verdict_reserve(gfal_scorer *s, size_t per_item, int *items)
+{
+    size_t budget = (size_t)1024 << 20;
+    if (const char *env = getenv("GFAL_VERDICT_SCRATCH_MB")) budget = (size_t)std::max(1, atoi(env)) << 20;
+    int n = (int)std::min<size_t>((size_t)std::max(*items, 1), std::max<size_t>(1, budget / per_item));
+    for (;; n = (n + 1) / 2) {
+        const size_t want = (size_t)n * per_item;
+        if (s->d_verdict && want <= s->verdict_cap) break;
+        if (s->d_verdict) HIP_TRY(hipFree(s->d_verdict));
+        s->d_verdict = nullptr;
+        s->verdict_cap = 0;
+        if (hipMalloc(reinterpret_cast<void **>(&s->d_verdict), want) == hipSuccess) {
+            s->verdict_cap = want;
+            break;
+        }
+        (void)hipGetLastError();
+        if (n == 1) {
+            set_err("verdicts: no room for the planes of one item (%zu bytes)", per_item);
+            return GFAL_E_NOMEM;
+        }
+    }
+    *items = n;
+    return GFAL_OK;
+}
+
+// Runs the batch (already checked) over the items in slabs of at most `per_slab`; for every
+// slab that `want(lo, hi)` accepts, the planes are left in s->d_verdict and `use(lo, hi)`
+// enqueues what reads them.  The paths' slot order is in s->d_order.
+static int verdict_slabs(gfal_scorer *s, const int32_t *path_off, const int32_t *path_steps, int32_t P,
+                         int32_t max_len, int filter, int per_slab, const std::function<bool(int, int)> &want,
+                         const std::function<int(int, int)> &use)
+{
+    const int64_t total = path_off[P];
+    const size_t n_in = (size_t)P + 1 + (size_t)total, n_out = (size_t)3 * P + 4;
+    int rc;
+    if (s->have_last) HIP_TRY(hipStreamSynchronize(s->last_stream));
+    if ((rc = dev_reserve(&s->d_path_off, &s->path_off_cap, n_in))) return rc;
+    if ((rc = dev_reserve(&s->d_counts, &s->counts_cap, n_out))) return rc;
+    HIP_TRY(hipMemcpy(s->d_path_off, path_off, ((size_t)P + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s->d_path_off + P + 1, path_steps, (size_t)total * sizeof(int32_t), hipMemcpyHostToDevice));
+    unsigned long long *planes = reinterpret_cast<unsigned long long *>(s->d_verdict);
+    for (int lo = 0; lo < s->n_items;) {
+        const int hi = std::min(s->n_items, lo + per_slab);
+        if (!want(lo, hi)) {
+            lo = hi;
+            continue;
+        }
+        HIP_TRY(hipMemsetAsync(planes, 0, (size_t)2 * P * (hi - lo) * sizeof(unsigned long long), s->stream));
+        ExtraCtx cx;
+        cx.mode = 3;
+        cx.planes = planes;
+        cx.item_lo = lo;
+        cx.item_hi = hi;
+        uint32_t *status_copy = s->d_counts + (size_t)3 * P;
+        if ((rc = score_device_impl(s, s->d_path_off, s->d_path_off + P + 1, P, total, max_len, filter,
+                                    s->d_counts, s->stream, status_copy, &cx)))
+            return rc;
+        uint32_t st4[4];
+        HIP_TRY(hipMemcpyAsync(st4, status_copy, sizeof(st4), hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipStreamSynchronize(s->stream));
+        rc = status_to_code(s, st4);
+        if (rc == GFAL_E_NOMEM) {
+            // exact-DP worklist overflow: grow it to the slab's need and run the slab
+            // again, or -- a need beyond the list's limit -- take half the slab
+            const unsigned long long need = (unsigned long long)st4[2] | ((unsigned long long)st4[3] << 32);
+            ++s->n_overflow_reruns;
+            if (grow_worklist(s, need) == GFAL_OK) continue;
+            if (hi - lo == 1) return GFAL_E_NOMEM;
+            per_slab = std::max(1, (hi - lo) / 2);
+            continue;
+        }
+        if (rc) return rc;
+        if ((rc = use(lo, hi))) return rc;
+        HIP_TRY(hipGetLastError());
+        lo = hi;
+    }
+    return GFAL_OK;
+}
+
+static int verdicts_impl(gfal_scorer *s, const int32_t *path_off, const int32_t *path_steps, int32_t P,
+                         int filter, int64_t k0, int64_t k1, uint8_t *codes)
+{
+    if (!s || P < 0) return GFAL_E_ARG;
+    if (k0 < 0 || k1 < k0 || k1 > s->n_aln_in) return GFAL_E_ARG;
+    if (P == 0) return GFAL_OK;
+    if (k1 > k0 && !codes) return GFAL_E_ARG;
+    int32_t max_len;
+    int rc = check_batch(s, path_off, path_steps, P, &max_len);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    if (k1 == k0) return GFAL_OK;
+    if ((rc = trace_tables(s))) return rc;
+
+    // the lanes the range needs (a copy of a dedup scorer: its representative's), sorted;
+    // zero-step alignments are good for every path and need none
+    const bool dedup = !s->rep_of.empty();
+    std::vector<std::pair<int32_t, int64_t>> order;
+    for (int64_t k = k0; k < k1; ++k) {
+        if (!s->owned[(size_t)k]) continue;
+        const int32_t slot = s->slot_of[(size_t)(dedup ? s->rep_of[(size_t)k] : k)];
+        if (slot < 0) memset(codes + (size_t)(k - k0) * P, 0, (size_t)P);
+        else order.emplace_back(slot, k);
+    }
+    if (order.empty()) return GFAL_OK;
+    std::sort(order.begin(), order.end());
+    std::vector<uint32_t> uslot;         // distinct lanes, ascending
+    std::vector<uint32_t> first_k;       // order[] index of each distinct lane's first alignment
+    for (size_t i = 0; i < order.size(); ++i)
+        if (i == 0 || order[i].first != order[i - 1].first) {
+            uslot.push_back((uint32_t)order[i].first);
+            first_k.push_back((uint32_t)i);
+        }
+    first_k.push_back((uint32_t)order.size());
+
+    // per item of a slab: its two planes and the codes of up to 64 lanes; the list of lanes
+    // once in front
+    const size_t planes_per_item = (size_t)2 * P * sizeof(unsigned long long);
+    const size_t per_item = planes_per_item + (size_t)WAVE * P + (size_t)WAVE * sizeof(uint32_t);
+    int per_slab = s->n_items;
+    if ((rc = verdict_reserve(s, per_item, &per_slab))) return rc;
+    unsigned char *base = s->d_verdict;
+    uint32_t *d_ent = reinterpret_cast<uint32_t *>(base + (size_t)per_slab * planes_per_item);
+    uint8_t *d_codes = reinterpret_cast<uint8_t *>(d_ent + (size_t)per_slab * WAVE);
+    std::vector<uint8_t> h_codes;
+    size_t e_lo = 0, e_hi = 0;           // distinct lanes of the current slab
+    auto want = [&](int lo, int hi) {
+        e_lo = std::lower_bound(uslot.begin(), uslot.end(), (uint32_t)lo * WAVE) - uslot.begin();
+        e_hi = std::lower_bound(uslot.begin(), uslot.end(), (uint32_t)hi * WAVE) - uslot.begin();
+        return e_hi > e_lo;
+    };
+    auto use = [&](int lo, int hi) -> int {
+        const uint32_t n_ent = (uint32_t)(e_hi - e_lo);
+        HIP_TRY(hipMemcpyAsync(d_ent, uslot.data() + e_lo, n_ent * sizeof(uint32_t), hipMemcpyHostToDevice,
+                               s->stream));
+        const long long cells = (long long)n_ent * P;
+        const unsigned blocks = (unsigned)std::min<long long>((cells + 255) / 256, 65536);
+        hipLaunchKernelGGL(k_verdict_codes, dim3(blocks), dim3(256), 0, s->stream,
+                           reinterpret_cast<const unsigned long long *>(base), (uint32_t)(hi - lo), (uint32_t)lo,
+                           (int)P, s->d_order, d_ent, n_ent, d_codes);
+        HIP_TRY(hipGetLastError());
+        h_codes.resize((size_t)cells);
+        HIP_TRY(hipMemcpyAsync(h_codes.data(), d_codes, (size_t)cells, hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipStreamSynchronize(s->stream));
+        for (size_t e = e_lo; e < e_hi; ++e)
+            for (uint32_t i = first_k[e]; i < first_k[e + 1]; ++i)
+                memcpy(codes + (size_t)(order[i].second - k0) * P, h_codes.data() + (e - e_lo) * P, (size_t)P);
+        return GFAL_OK;
+    };
+    rc = verdict_slabs(s, path_off, path_steps, P, max_len, filter, per_slab, want, use);
+    s->last_stream = s->stream;
+    s->have_last = true;
+    return rc;
+}
+
+static int discordance_impl(gfal_scorer *s, const int32_t *path_off, const int32_t *path_steps, int32_t P,
+                            int filter, uint32_t *d)
+{
+    if (!s || P < 0 || P > GFAL_MAX_COMPARE) return GFAL_E_ARG;
+    if (P == 0) return GFAL_OK;
+    if (!d) return GFAL_E_ARG;
+    int32_t max_len;
+    int rc = check_batch(s, path_off, path_steps, P, &max_len);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    memset(d, 0, (size_t)P * P * sizeof(uint32_t));
+    if (s->n_items == 0) return GFAL_OK;      // zero-step alignments are never bad
+
+    const bool weighted = s->d_item_weight != nullptr;
+    const int wbits = weighted ? 32 - __builtin_clz(s->max_weight) : 0;
+    const size_t planes_per_item = (size_t)2 * P * sizeof(unsigned long long);
+    const size_t per_item = planes_per_item + (size_t)wbits * sizeof(unsigned long long);
+    int per_slab = s->n_items;
+    if ((rc = verdict_reserve(s, per_item, &per_slab))) return rc;
+    if (s->have_last) HIP_TRY(hipStreamSynchronize(s->last_stream));
+    if ((rc = dev_reserve(&s->d_discord, &s->discord_cap, (size_t)P * P))) return rc;
+    HIP_TRY(hipMemsetAsync(s->d_discord, 0, (size_t)P * P * sizeof(uint32_t), s->stream));
+    const unsigned long long *planes = reinterpret_cast<const unsigned long long *>(s->d_verdict);
+    unsigned long long *wplanes = reinterpret_cast<unsigned long long *>(s->d_verdict + (size_t)per_slab * planes_per_item);
+    const unsigned tiles = (unsigned)((P + DISC_T - 1) / DISC_T);
+    auto use = [&](int lo, int hi) -> int {
+        const uint32_t n_words = (uint32_t)(hi - lo);
+        // enough workgroups to fill the CUs a few times over, each a few rounds of words
+        const uint32_t max_z = (n_words + DISC_WORDS - 1) / DISC_WORDS;
+        const uint32_t z = std::max(1u, std::min(max_z, (uint32_t)(8 * s->n_cus + tiles * tiles - 1) / (tiles * tiles)));
+        const uint32_t wpg = ((n_words + z - 1) / z + DISC_WORDS - 1) / DISC_WORDS * DISC_WORDS;
+        const uint32_t gz = (n_words + wpg - 1) / wpg;
+        if (weighted) {
+            hipLaunchKernelGGL(k_weight_planes, dim3((n_words * WAVE + 255) / 256), dim3(256), 0, s->stream,
+                               s->d_item_weight, (uint32_t)lo, n_words, wbits, wplanes);
+            hipLaunchKernelGGL(k_discord<true>, dim3(tiles, tiles, gz), dim3(DISC_THREADS), 0, s->stream, planes,
+                               n_words, (int)P, wplanes, wbits, wpg, s->d_order, s->d_discord);
+        } else {
+            hipLaunchKernelGGL(k_discord<false>, dim3(tiles, tiles, gz), dim3(DISC_THREADS), 0, s->stream, planes,
+                               n_words, (int)P, nullptr, 0, wpg, s->d_order, s->d_discord);
+        }
+        return GFAL_OK;
+    };
+    rc = verdict_slabs(s, path_off, path_steps, P, max_len, filter, per_slab,
+                       [](int, int) { return true; }, use);
+    s->last_stream = s->stream;
+    s->have_last = true;
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(d, s->d_discord, (size_t)P * P * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return GFAL_OK;
+}
+
+int gfal_scorer_verdicts(gfal_scorer *s, const int32_t *path_off, const int32_t *path_steps, int32_t n_paths,
+                         int filter, int64_t k0, int64_t k1, uint8_t *codes)
+{
+    return no_throw([&] { return verdicts_impl(s, path_off, path_steps, n_paths, filter, k0, k1, codes); });
+}
+
+int gfal_scorer_discordance(gfal_scorer *s, const int32_t *path_off, const int32_t *path_steps, int32_t n_paths,
+                            int filter, uint32_t *d)
+{
+    return no_throw([&] { return discordance_impl(s, path_off, path_steps, n_paths, filter, d); });
 }
 
 int gfal_scorer_get_info(gfal_scorer *s, gfal_info *out)

@@ -355,6 +355,40 @@ public:
         }
         return true;
     }
+    // verdicts of alignments [k0, k1) for every path of the batch, codes[(k - k0) * P + p]
+    // (gfal_scorer_verdicts); every shard writes the rows of its own alignments
+    bool verdicts(const std::vector<int32_t> &off, const std::vector<int32_t> &steps, bool filter, int64_t k0,
+                  int64_t k1, std::vector<uint8_t> &codes)
+    {
+        const size_t P = off.size() - 1;
+        codes.assign((size_t)(k1 - k0) * P, 0);
+        for (gfal_scorer *h : shards_) {
+            int err = gfal_scorer_verdicts(h, off.data(), steps.data(), (int32_t)P, filter ? 1 : 0, k0, k1,
+                                           codes.data());
+            if (err != GFAL_OK) {
+                fprintf(stderr, "Error: scorer: %s (%s)\n", gfal_strerror(err), gfal_last_error());
+                return false;
+            }
+        }
+        return true;
+    }
+    // d[i * P + j]: alignments good for path i and bad for path j, the shards' matrices summed
+    bool discordance(const std::vector<int32_t> &off, const std::vector<int32_t> &steps, bool filter,
+                     std::vector<uint32_t> &d)
+    {
+        const size_t P = off.size() - 1;
+        d.assign(P * P, 0);
+        std::vector<uint32_t> part(P * P);
+        for (gfal_scorer *h : shards_) {
+            int err = gfal_scorer_discordance(h, off.data(), steps.data(), (int32_t)P, filter ? 1 : 0, part.data());
+            if (err != GFAL_OK) {
+                fprintf(stderr, "Error: scorer: %s (%s)\n", gfal_strerror(err), gfal_last_error());
+                return false;
+            }
+            for (size_t i = 0; i < P * P; ++i) d[i] += part[i];
+        }
+        return true;
+    }
     int64_t n_aln() const { return n_aln_; }
     size_t n_shards() const { return shards_.size(); }
 

@@ -14,6 +14,9 @@ from . import build as _build
 
 GFAL_MAX_STEPS = 1000
 GFAL_STEP_OTHER = 0x40000000
+GFAL_MAX_COMPARE = 4096
+# gfal_scorer_verdicts codes
+VERDICT_GOOD, VERDICT_BAD, VERDICT_UNALIGNED = 0, 1, 2
 
 _i32p = ctypes.POINTER(ctypes.c_int32)
 _u32p = ctypes.POINTER(ctypes.c_uint32)
@@ -82,6 +85,10 @@ EXPORTS = {
                                                       ctypes.c_int64, ctypes.c_int64,
                                                       ctypes.POINTER(ctypes.c_int64),
                                                       ctypes.POINTER(ctypes.c_uint8)]),
+    "gfal_scorer_verdicts": (ctypes.c_int, [ctypes.c_void_p, _i32p, _i32p, ctypes.c_int32, ctypes.c_int,
+                                            ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_uint8)]),
+    "gfal_scorer_discordance": (ctypes.c_int, [ctypes.c_void_p, _i32p, _i32p, ctypes.c_int32, ctypes.c_int,
+                                               _u32p]),
     "gfal_scorer_set_profiling": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "gfal_scorer_get_info": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(GfalInfo)]),
 }
@@ -296,6 +303,33 @@ class Scorer:
             ops[np.arange(len(old_ops)) - old_off[owner] + ops_off[owner]] = old_ops
         self.pair_alignment_ops(path_steps, ops_off, ops)
         return fw, rc, ops_off, ops
+
+    def verdicts(self, path_off, path_steps, filter=True, k0=0, k1=None, out=None):
+        """uint8[k1 - k0, P]: the verdict of every (alignment, path) pair of the batch,
+        0 good, 1 bad, 2 unaligned (filter on and a node of the alignment is not on the
+        path).  A shard writes the rows of its own alignments only: pass the same `out`
+        to every shard of a set to fill it."""
+        path_off, path_steps = _i32(path_off), _i32(path_steps)
+        P = len(path_off) - 1
+        k1 = self.n_aln if k1 is None else k1
+        if out is None:
+            out = np.zeros((max(k1 - k0, 0), P), np.uint8)
+        assert out.dtype == np.uint8 and out.flags.c_contiguous and out.shape == (max(k1 - k0, 0), P)
+        _check(self._lib.gfal_scorer_verdicts(
+            self._h, _ptr(path_off, ctypes.c_int32), _ptr(path_steps, ctypes.c_int32), P,
+            int(bool(filter)), int(k0), int(k1), _ptr(out, ctypes.c_uint8)))
+        return out
+
+    def discordance(self, path_off, path_steps, filter=True):
+        """uint32[P, P]: d[i, j] = alignments of this shard good for path i and bad for
+        path j.  The matrices of the shards of a set add up."""
+        path_off, path_steps = _i32(path_off), _i32(path_steps)
+        P = len(path_off) - 1
+        d = np.zeros((P, P), np.uint32)
+        _check(self._lib.gfal_scorer_discordance(
+            self._h, _ptr(path_off, ctypes.c_int32), _ptr(path_steps, ctypes.c_int32), P,
+            int(bool(filter)), _ptr(d, ctypes.c_uint32)))
+        return d
 
     def set_profiling(self, on=True):
         """True / 1: events around every phase of a call; 2: around the dominant scan

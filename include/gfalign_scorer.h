@@ -289,6 +289,35 @@ int gfal_scorer_pair_alignment_lengths(gfal_scorer *s, const int32_t *path_steps
 int gfal_scorer_pair_alignment_ops(gfal_scorer *s, const int32_t *path_steps, int32_t n,
                                    int64_t k0, int64_t k1, const int64_t *ops_off, uint8_t *ops);
 
+/*
+ * Per-alignment verdicts of a batch of candidate paths: what src/eval.cpp:80-98 decides
+ * for every (alignment, path) pair before it counts.  Paths and filter as for
+ * gfal_scorer_score (GFAL_STEP_OTHER steps allowed).
+ *
+ * _verdicts: codes[(k - k0) * n_paths + p] for the alignments [k0, k1) of the caller's
+ *   numbering: 0 good, 1 bad, 2 unaligned (filter on and a node of the alignment is not
+ *   on the path).  A zero-step alignment is good for every path.  Per path, the 1s and
+ *   0s add up to gfal_scorer_score's bad and good; its `unaligned` counts the off-path
+ *   steps of the 2s (src/eval.cpp:86), not the 2s themselves.  A shard writes the
+ *   entries of its own alignments only; a copy in a gfal_scorer_create_dedup scorer gets
+ *   its representative's verdict.  GFAL_E_ARG also for k0 < 0, k1 > n_aln, k0 > k1.
+ * _discordance: d[i * n_paths + j] = alignments of the shard that are good for path i
+ *   and bad for path j (overwritten; the diagonal is 0).  The matrices of the shards of
+ *   one set add up (integer sums).  n_paths <= GFAL_MAX_COMPARE, else GFAL_E_ARG.
+ *
+ * Both run the batch pipeline with every decision kept as one good and one bad bit per
+ * (path, resident alignment), in slabs of alignments bounded by GFAL_VERDICT_SCRATCH_MB
+ * (default 1024, read at every call; 2 * n_paths / 8 bytes per alignment).  The slab
+ * shrinks on allocation failure; GFAL_E_NOMEM only when 64 alignments' worth cannot be
+ * had.  Both use the occurrence-chain scan whatever GFAL_SCAN says: a node set too large
+ * for its path images in LDS is GFAL_E_RANGE.
+ */
+#define GFAL_MAX_COMPARE 4096
+int gfal_scorer_verdicts(gfal_scorer *s, const int32_t *path_off, const int32_t *path_steps,
+                         int32_t n_paths, int filter, int64_t k0, int64_t k1, uint8_t *codes);
+int gfal_scorer_discordance(gfal_scorer *s, const int32_t *path_off, const int32_t *path_steps,
+                            int32_t n_paths, int filter, uint32_t *d);
+
 /* ---- introspection used by bench.py / tests; no effect on results ---- */
 
 typedef struct {
