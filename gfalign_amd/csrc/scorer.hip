@@ -2365,9 +2365,13 @@ __device__ __forceinline__ unsigned long long dilate_rows(uint32_t bits, int m)
 
 // Marks, in this lane's column of rowbits[][lane], the path positions whose node
 // occurs in the alignment: walks the occurrence chains of the m nodes (first[] /
-// next[] of the path image in HBM), all chains side by side.
+// next[] of the path image in HBM), all chains side by side.  Returns the lane's
+// 32-row blocks that hold rows to compute: the block of every marked row r and
+// the block of r + m (where its dilation ends), so that a block whose rows come
+// only from the previous block's carry is in the mask too.  Block 0 (the first
+// m rows) is the caller's.
 template <int MC>
-__device__ __forceinline__ void mark_match_rows(const uint16_t *__restrict__ img,
+__device__ __forceinline__ uint32_t mark_match_rows(const uint16_t *__restrict__ img,
                                                 const ImageLayout &L,
                                                 const uint32_t (&steps)[MC], int m,
                                                 uint32_t (*rowbits)[DP_THREADS], int lane)
@@ -2383,6 +2387,7 @@ __device__ __forceinline__ void mark_match_rows(const uint16_t *__restrict__ img
         const uint32_t head = first[j < m ? steps[j] >> 1 : 0u];   // index 0: always inside
         cur[j] = j < m ? head : ENT_NONE;
     }
+    uint32_t blocks = 0;
     while (true) {
         uint32_t nx[MC];
 #pragma unroll
@@ -2392,22 +2397,31 @@ __device__ __forceinline__ void mark_match_rows(const uint16_t *__restrict__ img
         for (int j = 0; j < MC; ++j) {
             const bool on = cur[j] < ENT_FOUND;        // a position, not a terminal
             const uint32_t pos = cur[j] & ENT_POS;
-            if (on) atomicOr(&rowbits[pos >> 5][lane], 1u << (pos & 31u));
+            if (on) {
+                atomicOr(&rowbits[pos >> 5][lane], 1u << (pos & 31u));
+                // (block 32 would lie beyond every path: block 31 stands in for it, exact)
+                blocks |= (1u << (pos >> 5)) | (1u << min((pos + (uint32_t)m) >> 5, 31u));
+            }
             any |= on;
             cur[j] = on ? nx[j] : ENT_NONE;
         }
         if (!WAVE_ANY(any)) break;
     }
+    return blocks;
 }
 
 // One orientation of one worklist entry per lane, rows in registers, only the
 // rows that can change the state.  `path_lds` holds the steps of the path most
 // lanes of the wave are on (`staged` lanes); the others read theirs from HBM.
+// `blocks` (mark_match_rows) lists the 32-row blocks that hold rows to compute:
+// a lane goes from one such block straight to the next, so an empty block costs
+// no turn of the loop.
 template <int MC>
 __device__ __forceinline__ int traceback_score_skip(const uint16_t *__restrict__ astep,
                                                     const uint16_t *path_lds, bool staged, int n,
                                                     const uint32_t (&b)[MC], int m,
-                                                    uint32_t (*rowbits)[DP_THREADS], int lane)
+                                                    uint32_t (*rowbits)[DP_THREADS], uint32_t blocks,
+                                                    int lane)
 {
     int c[MC + 1], up_add[MC];
 #pragma unroll
@@ -2423,10 +2437,14 @@ __device__ __forceinline__ int traceback_score_skip(const uint16_t *__restrict__
     int block = -1;                      // current 32-row block of the path
     uint32_t todo = 0;                   // its rows still to compute
     unsigned long long carry = (1ull << m) - 1ull;    // rows 1..m: the state is not steady yet
+    blocks |= 1u;                        // block 0: the first m rows
     bool done = n == 0;
     while (WAVE_ANY(!done)) {
         if (todo == 0 && !done) {
-            ++block;
+            // the next block with rows (a nonzero carry is always for block + 1, which
+            // the mask then holds: it is the block where a marked row's dilation ends)
+            block = blocks ? __builtin_ctz(blocks) : ROW_WORDS;
+            blocks &= blocks - 1u;
             if (block * 32 >= n) {
                 done = true;
             } else {
@@ -2461,7 +2479,7 @@ __device__ __forceinline__ bool dp_decide_regs(const uint16_t *__restrict__ aste
                                                const uint16_t *path_lds, bool staged, int n,
                                                const uint32_t (&fwd)[MC], const uint32_t (&rev)[MC],
                                                int m, bool has_fw, bool has_rc,
-                                               uint32_t (*rowbits)[DP_THREADS], int lane)
+                                               uint32_t (*rowbits)[DP_THREADS], uint32_t blocks, int lane)
 {
     uint32_t b[MC];
     // first orientation: fw if flagged, else rc
@@ -2471,13 +2489,13 @@ __device__ __forceinline__ bool dp_decide_regs(const uint16_t *__restrict__ aste
         const uint32_t v = first_rc ? (rev[j] ^ 1u) : fwd[j];
         b[j] = j < m ? v : STEP_INVALID;
     }
-    bool good = traceback_score_skip<MC>(astep, path_lds, staged, n, b, m, rowbits, lane) == 0 && n > 0;
+    bool good = traceback_score_skip<MC>(astep, path_lds, staged, n, b, m, rowbits, blocks, lane) == 0 && n > 0;
     const bool second = has_fw && has_rc;
     if (WAVE_ANY(second)) {
 #pragma unroll
         for (int j = 0; j < MC; ++j) b[j] = j < m ? (rev[j] ^ 1u) : STEP_INVALID;
         const int n2 = second ? n : 0;
-        good |= traceback_score_skip<MC>(astep, path_lds, staged, n2, b, m, rowbits, lane) == 0 && n2 > 0;
+        good |= traceback_score_skip<MC>(astep, path_lds, staged, n2, b, m, rowbits, blocks, lane) == 0 && n2 > 0;
     }
     return good;
 }
@@ -2768,9 +2786,10 @@ __global__ __launch_bounds__(DP_THREADS) void k_dp_regs(DpArgs a)
         __syncthreads();
         const bool staged = live && slot < STAGED_PATHS;
         const uint16_t *my_path = path_lds[staged ? slot : 0];
-        mark_match_rows<MC>(a.images + (size_t)e.p * a.L.total, a.L, fwd, e.m, rowbits, lane);
+        const uint32_t blocks =
+            mark_match_rows<MC>(a.images + (size_t)e.p * a.L.total, a.L, fwd, e.m, rowbits, lane);
         bool good = dp_decide_regs<MC>(e.astep, my_path, staged, e.n, fwd, rev, e.m, e.has_fw,
-                                       e.has_rc, rowbits, lane);
+                                       e.has_rc, rowbits, blocks, lane);
 #if defined(GFAL_ABLATE) && GFAL_ABLATE == 3
         good = false;
 #endif
